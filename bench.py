@@ -12,9 +12,19 @@ region runs step + gather back to back, so scaling is reported with and without 
   python bench.py [--gpus N] [--steps K] [--warmup W]      # spawns N ranks itself
   python bench.py --gpus 8 --global-batch 262144           # config 3 (32,768 per GPU)
   torchrun --nproc-per-node N bench.py --gpus N ...        # what the driver runs
+  python bench.py --full                                   # every secondary figure as well
+  python bench.py --dump-outputs DIR                       # the last step's arrays as .npy
 
 Default per-GPU batch is 65,536 (weak scaling); --global-batch fixes the total instead
 (strong scaling). Prints ONE JSON line on rank 0 (contract in the task statement).
+
+A plain run sets up, warms up, times --steps steps, writes its outputs if asked to and
+prints the headline line. --full adds what takes runs of its own: the step + gather
+region, the kernel-only and generic-kernel timings with the roofline figures, the gathered
+checksum and the CPU baseline. --dump-outputs DIR writes what the timed step returned to
+its caller in its last step (qfrc_inverse, config 5 its three Jacobians; each rank its
+shard) as DIR/<name>.npy; the inputs come from the seeded sampler, so two builds can be
+compared array for array.
 """
 import argparse
 import json
@@ -123,6 +133,29 @@ def cpu_baseline(m, args):
                     f"build on the first {k}: {same}"}
 
 
+DUMP_BYTES = 64 << 20           # --dump-outputs writes at most this much over all ranks
+
+
+def dump_outputs(path, arrays, world=1, rank=0):
+  """Write each array of `arrays` (name -> torch tensor or numpy array, float32/float64)
+  as path/<name>.npy, with more than one rank path/<name>_rank<r>.npy. An array over its
+  share of DUMP_BYTES is cut to a fixed, seeded sample of its rows (sorted indices in
+  path/<name>..._rows.npy as float64)."""
+  os.makedirs(path, exist_ok=True)
+  budget = DUMP_BYTES // world // max(len(arrays), 1)
+  for name, x in arrays.items():
+    x = x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+    assert x.dtype in (np.float32, np.float64), (name, x.dtype)
+    stem = os.path.join(path, name if world == 1 else f"{name}_rank{rank}")
+    if x.nbytes > budget:
+      row = max(x.nbytes // len(x), 1)
+      keep = max(budget // (row + 8), 1)      # 8: the row's index in _rows.npy
+      rows = np.sort(np.random.default_rng(20250314).choice(len(x), keep, replace=False))
+      np.save(stem + "_rows.npy", rows.astype(np.float64))
+      x = x[rows]
+    np.save(stem + ".npy", np.ascontiguousarray(x))
+
+
 def timed(fn, steps, world, dist, torch, dev):
   """Run fn `steps` times between barrier + device syncs; max wall time over ranks (s)."""
   torch.cuda.synchronize(dev)
@@ -157,6 +190,13 @@ def main():
                   help="instances in the CPU-baseline sample (rank 0, N=1 only; default "
                        "150k per thread, about 2-3 s of CPU work per thread)")
   ap.add_argument("--no-cpu", action="store_true")
+  ap.add_argument("--full", action="store_true",
+                  help="also measure what the headline does not need: the step + gather "
+                       "region, kernel-only and generic-kernel timings with the roofline, "
+                       "the gathered checksum and the CPU baseline")
+  ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                  help="after the timed steps, write the arrays the last step returned as "
+                       "DIR/<name>.npy (at most 64 MB in all)")
   ap.add_argument("--own-stream", action="store_true",
                   help="config 5: keep the context's own stream (ordered with torch's by "
                        "events around every call) instead of running it on torch's stream")
@@ -204,13 +244,51 @@ def main():
   def step():
     eng.inverse(count, out=out, mirror_input=True)
 
+  for _ in range(args.warmup):
+    step()
+  elapsed = timed(step, args.steps, world, dist, torch, dev)
+  if args.dump_outputs:
+    dump_outputs(args.dump_outputs, {"qfrc_inverse": out}, world, rank)
+  rec = None
+  if rank == 0:
+    rec = {
+        "metric": METRIC,
+        "value": total * args.steps / elapsed,
+        "unit": "evals/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong" if strong else "weak",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic: config-2 sampler (seed 20250314), inputs resident in HBM",
+        "config": {"workload": f"{args.model} 27-DoF mj_inverse (skipstage NONE), contacts "
+                               f"disabled, nefc=0, full mjData mirror written",
+                   "per_gpu_batch": count, "global_batch": total,
+                   "parallelism": f"dp{world}"},
+    }
+  if args.full:
+    full_figures(args, rec, eng, m, out, step, total, count, counts, world, rank, dist,
+                 torch, dev)
+  if rank == 0:
+    print(json.dumps(rec), flush=True)
+  eng.close()
+  if world > 1:
+    dist.destroy_process_group()
+
+
+def full_figures(args, rec, eng, m, out, step, total, count, counts, world, rank, dist,
+                 torch, dev):
+  """--full: the figures beside the headline, each from runs of its own after the timed
+  region, added to rank 0's result line `rec`."""
+  from mujoco_inversedynamicstest_amd import codegen, engine, parallel
+
   def step_gather():
     step()
     parallel.gather_to_rank0(out, world, rank, counts)
 
-  for _ in range(args.warmup):
-    step()
-  elapsed = timed(step, args.steps, world, dist, torch, dev)
   # the same steps followed by the gather of every rank's qfrc_inverse to rank 0
   step_gather()
   elapsed_g = timed(step_gather, args.steps, world, dist, torch, dev)
@@ -240,24 +318,7 @@ def main():
     cpu = cpu_baseline(m, args)
 
   if rank == 0:
-    value = total * args.steps / elapsed
-    rec = {
-        "metric": METRIC,
-        "value": value,
-        "unit": "evals/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong" if strong else "weak",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic: config-2 sampler (seed 20250314), inputs resident in HBM",
-        "config": {"workload": f"{args.model} 27-DoF mj_inverse (skipstage NONE), contacts "
-                               f"disabled, nefc=0, full mjData mirror written",
-                   "per_gpu_batch": count, "global_batch": total,
-                   "parallelism": f"dp{world}"},
+    rec.update({
         "with_gather": {"value": total * args.steps / elapsed_g,
                         "ms_per_step": elapsed_g / args.steps * 1e3,
                         "bytes_to_rank0_per_step": 8 * m.nv * (total - counts[0]),
@@ -284,11 +345,7 @@ def main():
                      "bytes_per_eval": bytes_per_eval},
         "cpu_baseline": cpu,
         "checksum_qfrc_inverse": checksum,
-    }
-    print(json.dumps(rec), flush=True)
-  eng.close()
-  if world > 1:
-    dist.destroy_process_group()
+    })
 
 
 def other_config(args):
@@ -312,6 +369,8 @@ def other_config(args):
     eng.inverse(B, mirror_input=True)
   torch.cuda.synchronize()
   dt = (time.perf_counter() - t0) / args.steps
+  if args.dump_outputs:       # the results of this path stay in the device mirror
+    dump_outputs(args.dump_outputs, {"qfrc_inverse": eng.field("qfrc_inverse", 0, B)})
   kernel_ms = eng.time_kernel(B, reps=max(args.steps, 10))
   ncon = eng.field_int("con_count", 0, B)[:, 0]
   nefc = eng.field_int("efc_count", 0, B)[:, 0]
@@ -389,6 +448,8 @@ def config5(args):
   for _ in range(args.warmup):
     step()
   dt = timed(step, args.steps, world, dist, torch, dev) / args.steps
+  if args.dump_outputs:
+    dump_outputs(args.dump_outputs, dict(zip(("DfDq", "DfDv", "DfDa"), out)), world, rank)
   # gather of the Jacobians to rank 0 (RCCL point-to-point), outside the timed region
   jac = torch.stack(out[:3])
   torch.cuda.synchronize(dev)

@@ -4,8 +4,9 @@ mj_compareFwdInv on real mjModel/mjData structs with a real arena (SURVEY.md §8
 
 The adapter is compiled by __graft_entry__.build() against the reference's public headers
 (mjModel/mjData layout) together with the test harness's struct builder
-(tests/adapter_harness.c) and linked to libmjhip.so: integration/_build/libadapter_gpu.so.
-The GPU box has no reference headers and runs that built file. Checked against the CPU
+(tests/adapter_harness.c) and linked to libmjhip.so: oracle/_ref/libadapter_gpu.so. A
+machine without the reference's headers runs the file built where they exist (oracle/_ref
+travels with the tree); a missing file is a failure. Checked against the CPU
 oracle on the same states: counts exact, qfrc_inverse and the constraint rows to the
 north-star 1e-10, contacts to 1e-12, solver_fwdinv of mj_compareFwdInv to 1e-10; the
 position-skipping calls read and update the rows the adapter left in the arena.
@@ -25,7 +26,7 @@ from adapter_common import Adapter
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-LIB = os.path.join(ROOT, "integration", "_build", "libadapter_gpu.so")
+LIB = os.path.join(ROOT, "oracle", "_ref", "libadapter_gpu.so")
 RTOL = 1e-10
 
 

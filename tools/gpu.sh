@@ -4,7 +4,7 @@
 # Steps
 #   tests     pytest -m gpu (PYTEST_K: a -k filter; PYTEST_FILES: files instead of tests/)
 #   smoke     __graft_entry__.smoke()
-#   bench     the default bench line                         -> gpurun_out/bench.json
+#   bench     the bench line with every secondary figure (--full), printed
 #   c4 / c5   config 4 / config 5 bench lines                 -> gpurun_out/c4.json, c5.json
 #   c4trace / c5trace   config 4 / 5 under a rocprofv3 kernel trace + stats
 #             -> gpurun_out/prof_c4/, prof_c5/
@@ -35,8 +35,7 @@ for step in "$@"; do
         > gpurun_out/smoke.log 2>&1 || { tail -20 gpurun_out/smoke.log; exit 1; }
       tail -1 gpurun_out/smoke.log ;;
     bench)
-      timeout -k 10 300 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err || exit 1
-      cat gpurun_out/bench.json ;;
+      timeout -k 10 300 python bench.py --full || exit 1 ;;
     c4)
       timeout -k 10 120 python bench.py --config 4 --steps 20 --warmup 3 > gpurun_out/c4.json \
         2> gpurun_out/c4.err || exit 1
