@@ -318,6 +318,10 @@ MJHIP_API int mjhip_contextCapacity(const mjhipContext* c);
 /* name of the straight-line (model-specialized) kernel selected for the context's model by
  * signature, or NULL when the generic kernel runs */
 MJHIP_API const char* mjhip_contextFastKernel(const mjhipContext* c);
+/* static LDS in bytes of that kernel as compiled (hipFuncGetAttributes), 0 when the generic
+ * kernel runs. Context creation and mjhip_contextLoadKernel fail with MJHIP_ERR_MODEL when it
+ * exceeds 40,960 B, above which only three of its workgroups fit a CU. */
+MJHIP_API int mjhip_contextFastKernelLds(const mjhipContext* c);
 /* Run-time specialization: load a straight-line kernel generated for this
  * context's model after the library was built. `image` is a gfx950 code object (hipcc
  * --genco of codegen.py's source for the model, mujoco_inversedynamicstest_amd/

@@ -71,6 +71,18 @@ VA_RECOMPUTE = False
 # values live across pos's post-order push k_all from 20 B to 1,968 B of scratch per lane
 # (tools/kernel_resources.py), and every spill reload waits for the store stream.
 QM_FORWARD = False
+# The va stage's tree pass keeps the cdof of the dofs on the current root-to-body path in an
+# LDS stack (written at a body's pre-visit, read back for the projections at its post-visit)
+# instead of re-reading them from the mirror. The stack shares k_all's trig region, which is
+# dead once the pos stage ends. None: as many slots as keep k_all's static LDS within
+# LDS_BUDGET (va_lds_capacity); an int forces the capacity (0: every projection re-reads, the
+# earlier behaviour). generate()'s va_slots argument overrides it per call.
+VA_LDS_SLOTS = None
+# the va stage keeps the qfrc_passive values it stores in registers for the assembly at the
+# post-visits instead of re-reading them from the mirror
+VA_KEEP_QFP = True
+# static LDS a k_all workgroup may hold while four of them share a CU's 160 KB
+LDS_BUDGET = 40960
 LANES = {"pos": 64, "fac": 64, "va": 64}
 # k_all's workgroup: ALL_LANES lanes (64 = one instance block per wave; 32 = each block split
 # over two half-filled waves, so batch 65,536 is 2,048 waves) and the waves per SIMD it is
@@ -225,6 +237,9 @@ def fast_path_supported(m) -> str | None:
   for a in range(m.nu):
     if m.actuator_trntype[a] not in (0, 1, 2, 3, 4, 5):
       return "unknown transmission"
+  if 8 * sum(_lds_doubles(m, 0)) > LDS_BUDGET:
+    # hinge sin/cos and the row-major output block: a fourth workgroup would not fit the CU
+    return "k_all's LDS over budget (hinges and dofs)"
   return None
 
 
@@ -309,10 +324,64 @@ def constraint_mode(m) -> str:
 CONSTRAINT_MODES = {"none": 0, "list": 1, "all": 2}
 
 
+def const_cdof(m, k):
+  """cdof of dof k where it is a model constant -- a free joint's translational dofs,
+  [0, 0, 0, e_k] (mj_comPos, engine_core_smooth.c:230-234) -- else None."""
+  j = int(m.dof_jntid[k])
+  c = k - int(m.jnt_dofadr[j])
+  if int(m.jnt_type[j]) != FREE or c >= 3:
+    return None
+  return [0.0] * 3 + [1.0 if r == c else 0.0 for r in range(3)]
+
+
+def va_slot_plan(m, capacity):
+  """The va stage's cdof stack: ({dof: slot}, deepest path's slot count). A dof's slot is its
+  index among the non-constant dofs (const_cdof) on its root-to-body path, so two dofs live
+  on one path at the same time never share one; dofs at or past `capacity` get none and keep
+  the re-read from the mirror."""
+  slot, depth = {}, {0: 0}
+  for b in range(1, m.nbody):
+    n = depth[int(m.body_parentid[b])]
+    for k in range(int(m.body_dofadr[b]), int(m.body_dofadr[b]) + int(m.body_dofnum[b])):
+      if const_cdof(m, k) is not None:
+        continue
+      if n < capacity:
+        slot[k] = n
+      n += 1
+    depth[b] = n
+  return slot, max(depth.values())
+
+
+def _lds_doubles(m, slots, nl=None):
+  """(trig region, qo_lds) doubles per k_all workgroup of nl lanes with a cdof stack of
+  `slots` slots: trig and the stack share one region sized the larger of the two."""
+  nl = ALL_LANES if nl is None else nl
+  hinges = sum(1 for j in range(m.njnt) if int(m.jnt_type[j]) == HINGE)
+  ntrig = 2 * hinges if 0 < hinges <= MAX_LDS_HINGES else 0
+  return max(1, max(ntrig, 6 * slots) * nl), nl * max(m.nv, 1)
+
+
+def va_lds_capacity(m) -> int:
+  """The largest slot count (no more than the deepest path needs) for which k_all's static
+  LDS stays within LDS_BUDGET. The humanoid: (40,960 - 13,824 B of qo_lds) / 3,072 B per
+  slot = 8, a region of 24,576 B where trig alone took 21,504 B."""
+  depth = va_slot_plan(m, 0)[1]
+  n = depth
+  while n > 0 and 8 * sum(_lds_doubles(m, n)) > LDS_BUDGET:
+    n -= 1
+  return n
+
+
+def k_all_lds_bytes(m, va_slots=None) -> int:
+  """Static LDS of k_all_<name> (trig/stack region + qo_lds), as generate() declares it."""
+  M = _Model(m, va_slots)
+  return 8 * sum(_lds_doubles(m, M.va_nslot))
+
+
 class _Model:
   """Model constants the emitters share."""
 
-  def __init__(self, m):
+  def __init__(self, m, va_slots=None):
     self.m = m
     self.nbody, self.nv, self.nq, self.njnt = m.nbody, m.nv, m.nq, m.njnt
     self.parent = [int(x) for x in m.body_parentid]
@@ -345,6 +414,15 @@ class _Model:
     # 4 waves per CU must fit in 160 KB)
     hinges = [j for j in range(m.njnt) if int(m.jnt_type[j]) == HINGE]
     self.trig = {j: h for h, j in enumerate(hinges)} if 0 < len(hinges) <= MAX_LDS_HINGES else {}
+    # the va stage's cdof stack (VA_LDS_SLOTS): dof -> slot, and the slots the region holds
+    if va_slots is None:
+      va_slots = VA_LDS_SLOTS
+    if va_slots is None:
+      va_slots = va_lds_capacity(m)
+    if VA_RECOMPUTE and FUSE:
+      va_slots = 0          # that experiment reads trig throughout the va stage
+    self.va_slot, depth = va_slot_plan(m, va_slots)
+    self.va_nslot = min(va_slots, depth)
     self.spatial = set(spatial_tendons(m))
     self.ten_terms = []
     for t in range(m.ntendon):
@@ -1146,17 +1224,26 @@ def _gen_va(M: _Model, store_fields=None) -> str:
   for j in range(M.njnt):
     if m.jnt_actgravcomp[j]:
       actgc.update(range(int(m.jnt_dofadr[j]), int(m.jnt_dofadr[j]) + M.jnt_ndof(j)))
+  # the value stored as qfrc_passive stays in qfp[] for the assembly at the dof's body's
+  # post-visit (raw-RNE models, cmode 'all', never read it there)
+  keep_qfp = VA_KEEP_QFP and M.cmode != "all"
+  if keep_qfp:
+    E(f"double qfp[{nv}];")
   for dof in range(nv):
     G.st("qfrc_spring", dof, f"qfs[{dof}]")
     G.st("qfrc_damper", dof, f"qfd[{dof}]")
     G.st("qfrc_gravcomp", dof, f"qfg[{dof}]")
     G.st("qfrc_fluid", dof, "0.0")
     if dsbl & (1 << 5):
-      G.st("qfrc_passive", dof, "0.0")
+      passive = "0.0"
     elif has_gravcomp and dof not in actgc:
-      G.st("qfrc_passive", dof, f"(qfs[{dof}] + qfd[{dof}]) + qfg[{dof}]")
+      passive = f"(qfs[{dof}] + qfd[{dof}]) + qfg[{dof}]"
     else:
-      G.st("qfrc_passive", dof, f"qfs[{dof}] + qfd[{dof}]")
+      passive = f"qfs[{dof}] + qfd[{dof}]"
+    if keep_qfp:
+      E(f"qfp[{dof}] = {passive};")
+      passive = f"qfp[{dof}]"
+    G.st("qfrc_passive", dof, passive)
 
   # mj_comVel (:1833-1896) and both mj_rne calls (:1969-2023) in one tree pass
   E("// ---- tree pass: mj_comVel + mj_rne(flg_acc=0) + mj_rne(flg_acc=1)")
@@ -1174,6 +1261,11 @@ def _gen_va(M: _Model, store_fields=None) -> str:
   _gravity_acc(M, E)
   E("double acca_0[6]; mjh::copy(acca_0, cacc_0, 6);")
   E(f"double qacc[{nv}];")
+  # the cdof stack of the current path (VA_LDS_SLOTS), in the pos stage's trig region
+  slot = M.va_slot
+  sl, ss = _ll("va")[0], _ll("va")[1]
+  if slot:
+    E("double* const cstk = trig;")
   # row-major qfrc_inverse copy, or (no output array) a harmless second write of the mirror
   # slot: a select instead of a branch keeps the pass one scheduling region
   # the row-major qfrc_inverse copy goes through LDS (qo_lds[lane][k]); the kernel wrapper
@@ -1223,6 +1315,9 @@ def _gen_va(M: _Model, store_fields=None) -> str:
     E.open(f"{{  // body {i}")
     if recompute:
       recompute_body(i)
+    for k in range(bda, bda + dn):
+      if k in slot:
+        E(f"mjh::put6(cstk, {slot[k]}, {ss}, {sl}, cdof_{k});")
     E(f"double cvel_{i}[6];")
     E(f"mjh::copy(cvel_{i}, cvel_{p}, 6);")
     j = 0
@@ -1290,13 +1385,16 @@ def _gen_va(M: _Model, store_fields=None) -> str:
     # (engine_core_smooth.c:2008-2022); qfrc_inverse += armature*qacc - passive - constraint
     cd = "cdofp"
     for k in range(M.bdofadr[i], M.bdofadr[i] + M.bdofnum[i]):
+      if k in slot:
+        E(f"mjh::get6({cd}_{k}, cstk, {slot[k]}, {ss}, {sl});")
+    for k in range(M.bdofadr[i], M.bdofadr[i] + M.bdofnum[i]):
       G.st("qfrc_bias", k, f"mjh::dot6({cd}_{k}, cfrc_{i})")
       E.open()
       E(f"double qfi = mjh::dot6({cd}_{k}, frca_{i});")
       if M.cmode == "all":     # raw rne: k_constraint assembles every instance
         G.st("qfrc_inverse", k, "qfi")
       else:
-        E(f"const double qfa = qfi + ({lit(m.dof_armature[k])} * qacc[{k}] - qfp_{k} - 0.0);")
+        E(f"const double qfa = qfi + ({lit(m.dof_armature[k])} * qacc[{k}] - {qfp(k)} - 0.0);")
         if M.cmode == "list":
           E("qfi = cflag ? qfi : qfa;")
         else:
@@ -1310,20 +1408,36 @@ def _gen_va(M: _Model, store_fields=None) -> str:
       E(f"mjh::addTo(frca_{M.parent[i]}, frca_{i}, 6);")
     E.close()
 
+  def qfp(k):
+    return f"qfp[{k}]" if keep_qfp else f"qfp_{k}"
+
+  def cdof_decl(nm, k):
+    """cdof of dof k under the name nm: a literal where it is a model constant."""
+    c = const_cdof(m, k)
+    return f"double {nm}_{k}[6];" if c is None else f"const double {nm}_{k}[6] = {arr_lit(c)};"
+
   def loads(kind, i):
     dofs = range(M.bdofadr[i], M.bdofadr[i] + M.bdofnum[i])
     if recompute and kind == "pre":     # cinert and cdof recomputed, qacc from the mirror
       return [], [(f"qacc[{k}]", "qacc", k) for k in dofs]
     if kind == "pre":
-      decls = [f"double cinert_{i}[10];"] + [f"double cdof_{k}[6];" for k in dofs]
+      decls = [f"double cinert_{i}[10];"] + [cdof_decl("cdof", k) for k in dofs]
       ld = _vec_loads(f"cinert_{i}", "cinert", 10 * i, 10)
       for k in dofs:
-        ld += _vec_loads(f"cdof_{k}", "cdof", 6 * k, 6) + [(f"qacc[{k}]", "qacc", k)]
-    else:   # the projections reload cdof rather than keeping it live along the path
-      decls = [f"double cdofp_{k}[6], qfp_{k};" for k in dofs]
+        if const_cdof(m, k) is None:
+          ld += _vec_loads(f"cdof_{k}", "cdof", 6 * k, 6)
+        ld += [(f"qacc[{k}]", "qacc", k)]
+    else:
+      # the projections take cdof from the path's LDS stack; a dof past its capacity reloads
+      # it from the mirror rather than keeping it live along the path
+      decls = [cdof_decl("cdofp", k) for k in dofs]
       ld = []
       for k in dofs:
-        ld += _vec_loads(f"cdofp_{k}", "cdof", 6 * k, 6) + [(f"qfp_{k}", "qfrc_passive", k)]
+        if k not in slot and const_cdof(m, k) is None:
+          ld += _vec_loads(f"cdofp_{k}", "cdof", 6 * k, 6)
+        if not keep_qfp and M.cmode != "all":
+          decls.append(f"double qfp_{k};")
+          ld += [(f"qfp_{k}", "qfrc_passive", k)]
     return decls, ld
 
   _prefetched_dfs(G, loads, pre, post, PREFETCH)
@@ -1501,7 +1615,8 @@ _GEN = {"pos": lambda M, sf: _gen_pos(M, sf), "fac": lambda M, sf: _gen_fac(M, s
         "va": lambda M, sf: _gen_va(M, sf)}
 
 
-def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bool = False) -> str:
+def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bool = False,
+             va_slots=None) -> str:
   """HIP source of the four stage kernels of model `m` (skipstage = mjSTAGE_NONE).
 
   Also emits `fast_body_<name>`, which runs the four stage bodies for one instance in
@@ -1512,11 +1627,17 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
   translation unit than the registry, generate_registries).
   extern_c: give k_all_<name> C linkage (a run-time code object, specialize.py, whose
   kernel mjhip_contextLoadKernel looks up by name).
+  va_slots: capacity of the va stage's cdof stack (default VA_LDS_SLOTS).
   """
   why = fast_path_supported(m)
   if why:
     raise ValueError(f"model '{name}' cannot use the straight-line kernels: {why}")
-  M = _Model(m)
+  M = _Model(m, va_slots)
+  # the region the pos stage's trig and the va stage's cdof stack share, and qo_lds, in
+  # doubles per 64 lanes; every wrapper that runs the va body declares the region
+  nreg64 = _lds_doubles(m, M.va_nslot, 64)[0]
+  assert 8 * sum(_lds_doubles(m, M.va_nslot)) <= LDS_BUDGET, \
+      f"k_all_{name}: {8 * sum(_lds_doubles(m, M.va_nslot))} B of LDS, three workgroups per CU"
   bodies = {st: _GEN[st](M, store_fields) for st in STAGES}
   if NT_STORES:
     import re
@@ -1564,7 +1685,7 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
     double* __restrict__ qfrc_out, int* __restrict__ status, int* __restrict__ worklist,
     int* __restrict__ worklist_count, int* __restrict__ worklist_next,
     int* __restrict__ efc_count) {{
-  double trig[{max(1, 2 * len(M.trig) * 64)}];   // LDS on the device (k_pos)
+  double trig[{nreg64}];   // LDS on the device (k_pos's trig, then k_va's cdof stack)
   double qo_lds[{64 * max(M.nv, 1)}];             // LDS on the device (k_va)
   double qmr[{max(1, m.nM)}];                        // registers on the device (k_all)
   const bool fd = mr.fd_elide && blk >= mr.full_blk;   // mjd_inverseFD's perturbed blocks
@@ -1590,8 +1711,12 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
     elif st == "va":
       params = params.replace(", double* __restrict__ qo_lds", "")
       params = params.replace(", double* __restrict__ trig", "")
-      args = args.replace(", trig", ", nullptr")   # staged k_va: no LDS trig (not fused)
+      # staged k_va: no LDS trig (not fused), a region of its own for the cdof stack
       decl = f"  __shared__ double qo_lds[{nl * max(M.nv, 1)}];\n"
+      if M.va_slot:
+        decl += f"  __shared__ double trig[{6 * M.va_nslot * nl}];\n"
+      else:
+        args = args.replace(", trig", ", nullptr")
       if M.cmode != "all":   # coalesced row-major copy of the workgroup's qfrc_inverse rows
         tail = (f"  if (!qfrc_out) return;\n  __syncthreads();\n"
                 f"  const long r0 = (long)blockIdx.x*{nl};\n"
@@ -1615,8 +1740,11 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
   if nl != 64:
     assert all(LANES[st] == nl for st in STAGES), "stage LDS indexing must match ALL_LANES"
   sub = 64 // nl
-  ntrig = max(1, 2 * len(M.trig) * nl)
-  nqo = nl * max(M.nv, 1)
+  ntrig, nqo = _lds_doubles(m, M.va_nslot, nl)
+  # kernels that run the va body without the pos stage before it (64 lanes each) hold the
+  # cdof stack in an array of their own
+  stk_decl = f"  __shared__ double trig[{6 * M.va_nslot * 64}];\n" if M.va_slot else ""
+  stk_arg = "trig" if M.va_slot else "nullptr"
   fuse_tail = ""
   if M.cmode != "all":
     fuse_tail = (f"  if (!qfrc_out) return;\n  __syncthreads();\n"
@@ -1675,7 +1803,7 @@ __global__ __launch_bounds__(64, 1) void k_spos_{name}(Mirror mr, int B,
     const double* __restrict__ qacc_in, int* __restrict__ worklist,
     int* __restrict__ worklist_count, int* __restrict__ worklist_next,
     int* __restrict__ efc_count) {{
-  __shared__ double trig[{ntrig}];
+  __shared__ double trig[{_lds_doubles(m, 0, 64)[0]}];
   MJH_PHASE0(19, 27);
   fast_pos_{name}<SV>(mr, blockIdx.x, threadIdx.x, B, {pos_args});
 }}
@@ -1683,11 +1811,11 @@ template <bool SV>
 __global__ __launch_bounds__(64, 1) void k_sfv_{name}(Mirror mr, int B,
     double* __restrict__ qfrc_out, int* __restrict__ status, int* __restrict__ efc_count) {{
   __shared__ double qo_lds[{nqo}];
-  MJH_PHASE(20);     // the position span runs from k_spos's start to here (launch gap included)
+{stk_decl}  MJH_PHASE(20);     // the position span runs from k_spos's start to here (launch gap included)
   fast_fac_{name}<SV>(mr, blockIdx.x, threadIdx.x, B, efc_count, nullptr);
   asm volatile("" ::: "memory"); MJH_SCHED_FENCE(); MJH_PHASE(21);
   fast_va_{name}<SV>(mr, blockIdx.x, threadIdx.x, B, qfrc_out, status, efc_count, qo_lds,
-                     nullptr);
+                     {stk_arg});
   asm volatile("" ::: "memory"); MJH_SCHED_FENCE(); MJH_PHASE(22);
 }}
 {"" if shared else "static "}void launch_split_{name}(hipStream_t s, const Mirror& mr, int B, int part,
@@ -1737,6 +1865,8 @@ __global__ __launch_bounds__(64, 1) void k_sfv_{name}(Mirror mr, int B,
                        status, efc_count);
   }}
 }}""")
+  # (the skip kernels below are not emitted into a run-time code object: the library looks up
+  # only its k_all, mjhip_contextLoadKernel)
   # k_vaskip: the va stage of mj_inverseSkip(mjSTAGE_POS) for mjd_inverseFD's qvel and qacc
   # perturbations (engine_derivative_fd.c:646-699). Instance off + t reads every position-
   # stage output (the va pointers it never stores) from its centre instance
@@ -1745,7 +1875,7 @@ __global__ __launch_bounds__(64, 1) void k_sfv_{name}(Mirror mr, int B,
   # pipeline's bit for bit. Work-list models: a centre with limit rows sets *needfull, and
   # k_fd_gate (mjhip.hip) then opens the range of a second k_all over the qvel/qacc
   # perturbations, which runs their full pipeline.
-  if M.cmode in ("none", "list"):
+  if M.cmode in ("none", "list") and not extern_c:
     import re
     vb = bodies["va"]
     # the fields the va stage stores, as recorded by _Stage.st while emitting it; a store the
@@ -1773,7 +1903,7 @@ __global__ __launch_bounds__(64, 1) void k_sfv_{name}(Mirror mr, int B,
     out.append(f"MJH_HD void fast_vaskip_{name}(const Mirror& mr, int blk, int lane, int sblk, "
                f"int slane, int B, const int* __restrict__ ecs, int pa, int pv, double eps, "
                f"{_SIG['va'][0]}) {{\n{skip_body}\n}}\n")
-  if M.cmode in ("none", "list"):
+  if M.cmode in ("none", "list") and not extern_c:
     # the acceleration stage alone (mj_inverseSkip(mjSTAGE_VEL)): k_acc for batched calls, and
     # in k_fdskip for mjd_inverseFD's qacc perturbations, whose velocity-stage inputs (cvel,
     # cdof_dot, qfrc_passive) and position-stage inputs are their centre's
@@ -1794,7 +1924,7 @@ __global__ __launch_bounds__(64, 1) void k_sfv_{name}(Mirror mr, int B,
     out.append(f"MJH_HD void fast_accskip_{name}(const Mirror& mr, int blk, int lane, int sblk, "
                f"int slane, int B, const int* __restrict__ ecs, int pa, double eps, "
                f"{_SIG['va'][0]}) {{\n{acc_skip}\n}}\n")
-  if M.cmode in ("none", "list"):
+  if M.cmode in ("none", "list") and not extern_c:
     flag = ("  if (ecs[0] != 0) needfull[0] = 1;\n" if M.cmode == "list" else "")
     pos_call = _SIG["pos"][1].replace("worklist_next", "nullptr")
     fac_call, va_call = _SIG["fac"][1], _SIG["va"][1]
@@ -1805,14 +1935,14 @@ __global__ __launch_bounds__(64, 1) void k_sfv_{name}(Mirror mr, int B,
 __global__ __launch_bounds__(64, 1) void k_vaskip_{name}(Mirror mr, int B, int off,
     int per, int sstride, int* __restrict__ efc_count, int* __restrict__ needfull, double eps) {{
   __shared__ double qo_lds[{64 * max(M.nv, 1)}];
-  const long gi = (long)off + (long)blockIdx.x*64 + threadIdx.x;
+{stk_decl}  const long gi = (long)off + (long)blockIdx.x*64 + threadIdx.x;
   if (gi >= B) return;
   const long si = (gi - off) / per * sstride;
   const int j = (int)((gi - off) % per);
   const int* ecs = efc_count + (si >> 6)*4*64 + (si & 63);
 {flag}  fast_vaskip_{name}(mr, (int)(gi >> 6), (int)(gi & 63), (int)(si >> 6), (int)(si & 63), B,
                     ecs, j < {M.nv} ? j : -1, j < {M.nv} ? -1 : j - {M.nv}, eps, nullptr,
-                    nullptr, efc_count, qo_lds, nullptr);
+                    nullptr, efc_count, qo_lds, {stk_arg});
 }}
 {"" if shared else "static "}void launch_vaskip_{name}(hipStream_t s, const Mirror& mr, int B, int off, int per,
                                 int sstride, int* efc_count, int* needfull, double eps) {{
@@ -1882,7 +2012,7 @@ __global__ __launch_bounds__(64, 1) void k_fdall_{name}(Mirror mr, int B, int ni
   const int* ecs = efc_count + (si >> 6)*4*64 + (si & 63);
 {flag}  fast_vaskip_{name}(mr, (int)(gi >> 6), (int)(gi & 63), (int)(si >> 6), (int)(si & 63), ninst,
                     ecs, j < {nv} ? j : -1, j < {nv} ? -1 : j - {nv}, eps, nullptr,
-                    nullptr, efc_count, qo_lds, nullptr);
+                    nullptr, efc_count, qo_lds, {stk_arg});
 }}
 {linkage_fd}void launch_fdall_{name}(hipStream_t s, const Mirror& mr, int B, int ninst, int per,
                                double eps, int* worklist, int* worklist_count,
@@ -1905,7 +2035,7 @@ __global__ __launch_bounds__(64, 1) void k_fdall_{name}(Mirror mr, int B, int ni
 __global__ __launch_bounds__(64, 1) void k_fdskip_{name}(Mirror mr, int B, int off,
     int per, int sstride, int* __restrict__ efc_count, int* __restrict__ needfull, double eps) {{
   __shared__ double qo_lds[{64 * max(M.nv, 1)}];
-  const long nq = ((long)B - off) / 2;
+{stk_decl}  const long nq = ((long)B - off) / 2;
   const long t = (long)blockIdx.x*64 + threadIdx.x;
   if (t >= 2*nq) return;
   const bool vel = t < nq;
@@ -1915,7 +2045,7 @@ __global__ __launch_bounds__(64, 1) void k_fdskip_{name}(Mirror mr, int B, int o
   const int* ecs = efc_count + (si >> 6)*4*64 + (si & 63);
 {flag}  if (vel) {{
     fast_vaskip_{name}(mr, (int)(gi >> 6), (int)(gi & 63), (int)(si >> 6), (int)(si & 63), B,
-                      ecs, -1, j, eps, nullptr, nullptr, efc_count, qo_lds, nullptr);
+                      ecs, -1, j, eps, nullptr, nullptr, efc_count, qo_lds, {stk_arg});
   }} else {{
     fast_accskip_{name}(mr, (int)(gi >> 6), (int)(gi & 63), (int)(si >> 6), (int)(si & 63), B,
                        ecs, j, eps, nullptr, nullptr, efc_count, qo_lds, nullptr);
@@ -1971,6 +2101,16 @@ __global__ __launch_bounds__(64, 1) void k_acc_{name}(Mirror mr, int B,
       gb = "g, b" if LANES[st] == 64 else f"dim3(g.x*{64 // LANES[st]}), dim3({LANES[st]})"
       out.append(f"  hipLaunchKernelGGL(k_{st}_{name}, {gb}, 0, s, mr, B, {args});")
   out.append("}")
+  # the static LDS of the k_all variants, as compiled (mjhip_contextCreate's guard)
+  if FUSE and not extern_c:
+    out.append(f"{'' if shared else 'static '}int lds_fast_{name}() {{\n"
+               f"  hipFuncAttributes a;\n  size_t n = 0;")
+    for _, v in variants:
+      out.append(f"  if (hipFuncGetAttributes(&a, (const void*)k_all_{name}{v}) != hipSuccess) "
+                 f"return -1;\n  n = a.sharedSizeBytes > n ? a.sharedSizeBytes : n;")
+    out.append("  return (int)n;\n}")
+  else:
+    out.append(f"{'' if shared else 'static '}int lds_fast_{name}() {{ return 0; }}")
   out.append("#endif")
   if exact:
     out.append("#if defined(__clang__)\n#pragma clang fp contract(fast)\n#endif")
@@ -2046,6 +2186,7 @@ def generate_registries(entries) -> tuple:
                       "int*, int*, double);")
       main.append(f"void launch_skip_{name}(hipStream_t, const Mirror&, int, int, double*, "
                   "int*, int*);")
+      main.append(f"int lds_fast_{name}();")
       if constraint_mode(m) == "all":
         main.append(f"void launch_split_{name}(hipStream_t, const Mirror&, int, int, "
                     "const double*, const double*, const double*, int*, int*, int*);")
@@ -2059,10 +2200,10 @@ def generate_registries(entries) -> tuple:
     fdall = f"launch_fdall_{name}" if fdall_ok(m) else "nullptr"
     reg.append(f'  {{0x{fields.model_signature(m):016x}ull, launch_fast_{name}, "{name}", '
                f'{CONSTRAINT_MODES[constraint_mode(m)]}, {fns}, launch_skip_{name}, {split}, '
-               f'{fdall}}},')
+               f'{fdall}, lds_fast_{name}}},')
   main.append("static const FastKernelEntry g_fast_kernels[] = {")
   main.extend(reg)
-  main.append("  {0ull, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr}};")
+  main.append("  {0ull, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}};")
   return "\n".join(main) + "\n", "\n".join(exact) + "\n"
 
 
@@ -2079,8 +2220,8 @@ def generate_registry(entries) -> str:
     fdall = f"launch_fdall_{name}" if fdall_ok(m) else "nullptr"
     reg.append(f'  {{0x{fields.model_signature(m):016x}ull, launch_fast_{name}, "{name}", '
                f'{CONSTRAINT_MODES[constraint_mode(m)]}, {fns}, launch_skip_{name}, {split}, '
-               f'{fdall}}},')
+               f'{fdall}, lds_fast_{name}}},')
   out.append("static const FastKernelEntry g_fast_kernels[] = {")
   out.extend(reg)
-  out.append("  {0ull, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr}};")
+  out.append("  {0ull, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}};")
   return "\n".join(out) + "\n"

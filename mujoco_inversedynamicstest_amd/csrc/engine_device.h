@@ -519,6 +519,15 @@ template <class R> MJH_HD void pin(R r, int n) {
   for (int i = 0; i < n; i++) __asm__("" : "+v"(r[i]));
 #endif
 }
+// The straight-line va stage's cdof stack (codegen.py VA_LDS_SLOTS): slot s of a lane holds
+// one dof's cdof at stk[(s*6 + c)*stride + lane], so consecutive lanes hit consecutive LDS
+// banks. On the host the region is a plain array.
+template <class A> MJH_HD void put6(double* stk, int s, int stride, int lane, A a) {
+  for (int c = 0; c < 6; c++) stk[(s*6 + c)*stride + lane] = a[c];
+}
+template <class R> MJH_HD void get6(R r, const double* stk, int s, int stride, int lane) {
+  for (int c = 0; c < 6; c++) r[c] = stk[(s*6 + c)*stride + lane];
+}
 template <class R, class A> MJH_HD void scl(R r, A a, double s, int n) {
   for (int i = 0; i < n; i++) r[i] = a[i]*s;
 }

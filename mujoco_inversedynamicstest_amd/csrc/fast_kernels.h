@@ -41,7 +41,14 @@ struct FastKernelEntry {
   // efc_count, fdflag, the flags, the epoch); null where there is no k_vaskip
   void (*launch_fdall)(hipStream_t, const Mirror&, int, int, int, double, int*, int*, int*,
                        int*, int*, int*, int);
+  // static LDS in bytes of the compiled k_all variants (hipFuncGetAttributes), -1 on a HIP
+  // error; null for run-time kernels, whose code object mjhip_contextLoadKernel queries
+  int (*lds_bytes)();
 };
+
+// static LDS a k_all workgroup may hold while four of them share a CU's 160 KB
+// (codegen.py LDS_BUDGET)
+constexpr int kFastLdsBudget = 40960;
 
 // the bundled models' kernels (gen_fast.hip), terminated by an entry with launch = nullptr
 const FastKernelEntry* mjhip_fastKernels();

@@ -474,6 +474,7 @@ struct mjhipContext_ {
   int* status = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   const FastKernelEntry* fast = nullptr;   // straight-line kernel for this model, if any
+  int fast_lds = 0;                        // its k_all's static LDS (mjhip_contextFastKernelLds)
   int* worklist = nullptr;                 // capacity + 2 ints: [count0, count1, list...]
   int wl_parity = 0;                       // counter the next fast launch uses
   int wl_last = 0;                         // counter the last fast launch used
@@ -819,6 +820,18 @@ MJHIP_API int mjhip_contextCreateCapped(const mjhipModel* m, int device, int cap
       if (e->sig == c->sig) c->fast = e;
     }
   }
+  if (c->fast && c->fast->lds_bytes) {
+    // four k_all workgroups share a CU's LDS (one wave per SIMD): a kernel compiled over the
+    // budget would run on three SIMDs of each CU
+    c->fast_lds = c->fast->lds_bytes();
+    if (c->fast_lds < 0) return fail("hipFuncGetAttributes(k_all)");
+    if (c->fast_lds > kFastLdsBudget) {
+      set_error("kernel k_all_%s holds %d B of LDS, over the %d B that let four workgroups "
+                "share a CU", c->fast->name, c->fast_lds, kFastLdsBudget);
+      mjhip_contextFree(c);
+      return MJHIP_ERR_MODEL;
+    }
+  }
   // the cooperative constraint kernel's pair program (16 lanes per instance: 8 and 32 were
   // slower, profiles/r02/bench_c4_L*.json; MJHIP_COOP_LANES=0 selects the one-lane
   // k_constraint)
@@ -973,6 +986,19 @@ MJHIP_API int mjhip_contextLoadKernel(mjhipContext* c, const void* image, size_t
     set_error("mjhip_contextLoadKernel: no kernel '%s' in the code object", kname.c_str());
     return MJHIP_ERR_HIP;
   }
+  int lds = 0;
+  if (hipFuncGetAttribute(&lds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, fn) != hipSuccess) {
+    hipModuleUnload(mod);
+    set_error("mjhip_contextLoadKernel: hipFuncGetAttribute('%s') failed", kname.c_str());
+    return MJHIP_ERR_HIP;
+  }
+  if (lds > kFastLdsBudget) {
+    hipModuleUnload(mod);
+    set_error("mjhip_contextLoadKernel: kernel '%s' holds %d B of LDS, over the %d B that let "
+              "four workgroups share a CU", kname.c_str(), lds, kFastLdsBudget);
+    return MJHIP_ERR_MODEL;
+  }
+  c->fast_lds = lds;
   if (c->rt_module) hipModuleUnload(c->rt_module);
   c->rt_module = mod;
   c->rt_fn = fn;
@@ -1076,6 +1102,10 @@ MJHIP_API int mjhip_contextCapacity(const mjhipContext* c) { return c ? c->capac
 
 MJHIP_API const char* mjhip_contextFastKernel(const mjhipContext* c) {
   return (c && c->fast) ? c->fast->name : nullptr;
+}
+
+MJHIP_API int mjhip_contextFastKernelLds(const mjhipContext* c) {
+  return (c && c->fast) ? c->fast_lds : 0;
 }
 
 MJHIP_API int mjhip_contextLastPath(const mjhipContext* c) { return c ? c->last_path : -1; }

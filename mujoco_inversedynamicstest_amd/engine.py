@@ -52,6 +52,7 @@ SIGNATURES = {
     "mjhip_contextFree": (None, [_V]),
     "mjhip_contextCapacity": (ctypes.c_int, [_V]),
     "mjhip_contextFastKernel": (ctypes.c_char_p, [_V]),
+    "mjhip_contextFastKernelLds": (ctypes.c_int, [_V]),
     "mjhip_contextLoadKernel": (ctypes.c_int, [_V, _V, ctypes.c_size_t, ctypes.c_char_p,
                                                ctypes.c_ulonglong, ctypes.c_int]),
     "mjhip_worklistCount": (ctypes.c_int, [_V]),
@@ -250,6 +251,11 @@ class InverseEngine:
     """Name of the model-specialized kernel in use, or None (generic kernel)."""
     n = lib().mjhip_contextFastKernel(self.ctx)
     return n.decode() if n else None
+
+  @property
+  def fast_kernel_lds(self):
+    """Static LDS in bytes of the model-specialized kernel as compiled (0: generic kernel)."""
+    return lib().mjhip_contextFastKernelLds(self.ctx)
 
   @property
   def constraint_kernel(self):
