@@ -339,6 +339,20 @@ MJHIP_API int mjhip_contextLoadKernel(mjhipContext* c, const void* image, size_t
  * kernel beside the fac / va stages, joined by the assembly; opt-in with MJHIP_SPLIT=1);
  * -1 before any call */
 MJHIP_API int mjhip_contextLastPath(const mjhipContext* c);
+/* Model-constant output slots. Some mjData outputs of a straight-line kernel are numbers its
+ * generator holds as literals (the world body's frame, fixed-tendon Jacobians, joint
+ * transmission moments, a free joint's translational cdof rows, forces the model cannot
+ * have): the same in every instance and every call. The kernel does not store them per call;
+ * k_const_<name> writes them over the whole capacity before the context's first launch of
+ * generated code, and again after mjhip_contextLoadKernel and after any mjhip_mirrorUpload.
+ * mjhip_contextConstStores returns their count per instance (0: the generic kernel, or a
+ * kernel that stores everything itself); a code object without k_const_<name> is refused by
+ * mjhip_contextLoadKernel with MJHIP_ERR_MODEL. mjhip_contextConstLaunches counts the
+ * k_const launches of the context so far. The generic kernel stores the same values, so the
+ * paths mix freely. A write into such a slot through mjhip_mirrorDevicePtr is NOT restored:
+ * the library cannot see it (call mjhip_mirrorUpload on any field to have them rewritten). */
+MJHIP_API int mjhip_contextConstStores(const mjhipContext* c);
+MJHIP_API int mjhip_contextConstLaunches(const mjhipContext* c);
 /* the constraint kernel the context's last straight-line call launched, e.g.
  * "k_constraint_coop<16, false, true, false>" (the work-list kernel of a limits-only model) or
  * "k_constraint<true, true, false>"; "none" when it launched none (profiles name it) */
@@ -390,7 +404,8 @@ MJHIP_API int mjhip_fieldSizeInt(const mjhipContext* c, const char* field);
 MJHIP_API int mjhip_mirrorFieldSize(const mjhipContext* c, const char* field);
 MJHIP_API int mjhip_mirrorUpload(mjhipContext* c, const char* field, int first, int count,
                                  const mjtNum* src);
-/* device pointer of a mirror field (block layout above) */
+/* device pointer of a mirror field (block layout above). Writes through it into the
+ * model-constant output slots (mjhip_contextConstStores) are not restored by later calls. */
 MJHIP_API void* mjhip_mirrorDevicePtr(mjhipContext* c, const char* field);
 /* per-instance status words of the last call (device pointer, B ints) */
 MJHIP_API int mjhip_statusDownload(mjhipContext* c, int first, int count, int* dst);

@@ -3,7 +3,9 @@
 The generic kernel (csrc/engine_device.h) walks the model's arrays at run time and keeps
 every intermediate in the device mirror. This generator instead unrolls the reference's
 loops over the model's bodies, joints and dofs at build time. Model constants become exact
-literals, and every mjData output is stored to the mirror exactly once. Arithmetic goes
+literals, and every mjData output is stored to the mirror exactly once per call -- except the
+outputs that are themselves model constants, which k_const_<name> stores once per context
+(CONST_ONCE below). Arithmetic goes
 through the same helper templates as the generic kernel (mjh::mulQuat, mjh::inertCom,
 mjh::dot6, ...) in the same order, so the outputs are bit-identical to the generic kernel's
 and the oracle's (tests/test_codegen_cpu.py).
@@ -119,6 +121,13 @@ NT_LOAD_SV_STAGES = ("va",)
 # 8 x 64 cycles; 2^22 polls is about a second -- the flag is raised within the launch's
 # first hundred microseconds, as every centre block is dispatched before any waiting one)
 FD_WAIT_ITERS = 1 << 22
+# Stores whose value is a model constant -- a number this generator holds and prints as a
+# literal, the same in every instance and every call -- leave the stage bodies for
+# fast_const_<name>, which k_const_<name> runs once per context over the whole capacity (and
+# again after anything that may have overwritten the slots: mjhip.hip const_stale). Only
+# _Stage.st_const sites qualify, and only fields no other kernel of the context may write
+# with another value (_Model.const_ok). Off: the parent's text.
+CONST_ONCE = True
 
 
 # mjd_inverseFD's perturbed instances (mjhip_inverseFDBatch with a stage-skip layout, whose
@@ -424,6 +433,14 @@ class _Model:
     self.va_slot, depth = va_slot_plan(m, va_slots)
     self.va_nslot = min(va_slots, depth)
     self.spatial = set(spatial_tendons(m))
+    # CONST_ONCE: {(field, index): expression} in emission order, and the declarations the
+    # expressions name
+    self.consts, self.const_decls = {}, []
+    g = np.asarray(m.opt["gravity"], dtype=float)
+    self.has_gravcomp = bool(m.ngravcomp and not (self.dsbl & (1 << 5)) and
+                             not (self.dsbl & (1 << 6)) and np.sqrt(g @ g) != 0)
+    self.has_fluid = (m.opt["density"] > 0 or m.opt["viscosity"] > 0) and \
+        not self.dsbl & (1 << 5)
     self.ten_terms = []
     for t in range(m.ntendon):
       adr, num = int(m.tendon_adr[t]), int(m.tendon_num[t])
@@ -433,6 +450,23 @@ class _Model:
       self.ten_terms.append([(float(m.wrap_prm[w]), int(m.jnt_qposadr[m.wrap_objid[w]]),
                               int(m.jnt_dofadr[m.wrap_objid[w]]))
                              for w in range(adr, adr + num)])
+
+  def const_ok(self, field) -> bool:
+    """Whether a generator-constant store of `field` may leave the stage bodies: no other
+    kernel of the context writes the field's slots with another value. The tendon pass
+    (post_pass.h tendonAfter) re-forms tendons, their transmissions and all of mj_passive,
+    the fluid pass qfrc_fluid; the constraint kernels write qfrc_constraint for the instances
+    they serve (and every efc_*/con_* field, which no st_const site names)."""
+    if not CONST_ONCE:
+      return False
+    if field in ("ten_J", "actuator_moment"):
+      return not self.spatial
+    if field in ("qfrc_fluid", "qfrc_gravcomp"):
+      return not self.spatial and not self.has_fluid
+    if field == "qfrc_constraint":
+      return self.cmode == "none"
+    return field in ("xpos", "xquat", "xmat", "xipos", "ximat", "geom_xpos", "geom_xmat",
+                     "site_xpos", "site_xmat", "cinert", "crb", "cdof", "cvel", "cdof_dot")
 
   def ten_row(self, t):
     assert t not in self.spatial, "spatial tendon rows are formed at run time"
@@ -480,6 +514,24 @@ class _Stage:
   def stv(self, field, k0, arr, n):
     for c in range(n):
       self.st(field, k0 + c, f"{arr}[{c}]")
+
+  def st_const(self, field, k, expr, decl=None):
+    """A store whose value the generator holds as a Python number: `expr` is its literal, or
+    names an array that `decl` declares from literals and nothing assigns afterwards. With
+    CONST_ONCE it goes to fast_const_<name> (same expression text) instead of this stage."""
+    if not self.M.const_ok(field):
+      self.st(field, k, expr)
+      return
+    if self.store_fields is not None and field not in self.store_fields:
+      return
+    M = self.M
+    assert M.consts.setdefault((field, k), expr) == expr, (field, k, expr)
+    if decl and decl not in M.const_decls:
+      M.const_decls.append(decl)
+
+  def stv_const(self, field, k0, arr, n, decl):
+    for c in range(n):
+      self.st_const(field, k0 + c, f"{arr}[{c}]", decl)
 
   def pointers(self, names):
     for nm in names:
@@ -643,11 +695,20 @@ def _emit_local2global(G: _Stage, dst_pos, dst_mat, pos, quat, body, sf, with_ma
   E.close()
 
 
+_WORLD_FRAME = ("double xpos_0[3] = {0.0, 0.0, 0.0}, xquat_0[4] = {1.0, 0.0, 0.0, 0.0};",
+                "double xmat_0[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};",
+                "double xipos_0[3] = {0.0, 0.0, 0.0};",
+                "double ximat_0[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};")
+# the world body's frame is these literals and nothing assigns them (the declaration each
+# st_const of a world-body store names)
+_WORLD_DECL = "\n".join(_WORLD_FRAME)
+_CRB0_DECL = "double crb_0[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};"
+_CVEL0_DECL = "double cvel_0[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};"
+
+
 def _world_frame(E):
-  E("double xpos_0[3] = {0.0, 0.0, 0.0}, xquat_0[4] = {1.0, 0.0, 0.0, 0.0};")
-  E("double xmat_0[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};")
-  E("double xipos_0[3] = {0.0, 0.0, 0.0};")
-  E("double ximat_0[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0};")
+  for line in _WORLD_FRAME:
+    E(line)
 
 
 def _camlight_needs(m):
@@ -741,7 +802,7 @@ def _gen_pos(M: _Model, store_fields=None) -> str:
       G.st("ten_length", t, f"ten_length[{t}]")
       J = M.ten_row(t)
       for k in range(nv):
-        G.st("ten_J", t * nv + k, lit(J[k]))
+        G.st_const("ten_J", t * nv + k, lit(J[k]))
   if m.nu:
     E("// ---- mj_transmission (hinge/slide/ball/free joint, fixed tendon)")
     for a in range(m.nu):
@@ -756,7 +817,8 @@ def _gen_pos(M: _Model, store_fields=None) -> str:
         G.st("actuator_length", a, f"ten_length[{jid}]*{lit(g)}")
         J = M.ten_row(jid)
         for k in range(int(m.moment_rownnz[a])):
-          G.st("actuator_moment", adr + k, lit(float(J[int(m.moment_colind[adr + k])]) * g))
+          G.st_const("actuator_moment", adr + k,
+                     lit(float(J[int(m.moment_colind[adr + k])]) * g))
         continue
       jt, qa = int(m.jnt_type[jid]), int(m.jnt_qposadr[jid])
       inparent = m.actuator_trntype[a] == 1
@@ -791,12 +853,12 @@ def _gen_pos(M: _Model, store_fields=None) -> str:
           E("mjh::copy3(ga, g3);")
         G.st("actuator_length", a, "0.0")
         for k in range(3):
-          G.st("actuator_moment", adr + k, lit(gear[k]))
+          G.st_const("actuator_moment", adr + k, lit(gear[k]))
         G.stv("actuator_moment", adr + 3, "ga", 3)
         E.close()
         continue
       G.st("actuator_length", a, f"qpos[{qa}]*{lit(g)}")
-      G.st("actuator_moment", adr, lit(g))
+      G.st_const("actuator_moment", adr, lit(g))
 
   cams = {}
   for c in range(m.ncam):
@@ -832,11 +894,26 @@ def _gen_pos(M: _Model, store_fields=None) -> str:
     E(f"double keep_xpos_{b}[3];")
   _world_frame(E)
 
+  def world_attached(kind, k, sf):
+    """A geom or site of the world body whose frame is a copy of the world's (sameframe 1:
+    the body frame, 2: the inertial frame): the literals themselves, stored as constants."""
+    if sf not in (1, 2) or not (M.const_ok(f"{kind}_xpos") and M.const_ok(f"{kind}_xmat")):
+      return False
+    G.stv_const(f"{kind}_xpos", 3 * k, "xpos_0" if sf == 1 else "xipos_0", 3, _WORLD_DECL)
+    G.stv_const(f"{kind}_xmat", 9 * k, "xmat_0" if sf == 1 else "ximat_0", 9, _WORLD_DECL)
+    return True
+
   def frame_outputs(i):
     """xipos/ximat, geom and site frames of body i (stored by whichever pass owns them)."""
-    G.stv("xipos", 3 * i, f"xipos_{i}", 3)
-    G.stv("ximat", 9 * i, f"ximat_{i}", 9)
+    if i:
+      G.stv("xipos", 3 * i, f"xipos_{i}", 3)
+      G.stv("ximat", 9 * i, f"ximat_{i}", 9)
+    else:
+      G.stv_const("xipos", 0, "xipos_0", 3, _WORLD_DECL)
+      G.stv_const("ximat", 0, "ximat_0", 9, _WORLD_DECL)
     for g in geoms.get(i, []):
+      if not i and world_attached("geom", g, int(m.geom_sameframe[g])):
+        continue
       E.open()
       _emit_local2global(G, "gp", "gm", m.geom_pos[g], m.geom_quat[g], i,
                          int(m.geom_sameframe[g]))
@@ -844,6 +921,8 @@ def _gen_pos(M: _Model, store_fields=None) -> str:
       G.stv("geom_xmat", 9 * g, "gm", 9)
       E.close()
     for s in sites.get(i, []):
+      if not i and world_attached("site", s, int(m.site_sameframe[s])):
+        continue
       E.open()
       _emit_local2global(G, "sp", "sm", m.site_pos[s], m.site_quat[s], i,
                          int(m.site_sameframe[s]))
@@ -858,9 +937,9 @@ def _gen_pos(M: _Model, store_fields=None) -> str:
       _emit_local2global(G, f"xipos_{i}", f"ximat_{i}", m.body_ipos[i], m.body_iquat[i], i,
                          int(m.body_sameframe[i]), with_mat=FRAMES_IN_PASS1)
     elif FRAMES_IN_PASS1:
-      G.stv("xpos", 0, "xpos_0", 3)
-      G.stv("xquat", 0, "xquat_0", 4)
-      G.stv("xmat", 0, "xmat_0", 9)
+      G.stv_const("xpos", 0, "xpos_0", 3, _WORLD_DECL)
+      G.stv_const("xquat", 0, "xquat_0", 4, _WORLD_DECL)
+      G.stv_const("xmat", 0, "xmat_0", 9, _WORLD_DECL)
     if FRAMES_IN_PASS1:
       frame_outputs(i)
     if i in need_xpos:
@@ -899,9 +978,9 @@ def _gen_pos(M: _Model, store_fields=None) -> str:
     else:
       _world_frame(E)
       if not FRAMES_IN_PASS1:
-        G.stv("xpos", 0, "xpos_0", 3)
-        G.stv("xquat", 0, "xquat_0", 4)
-        G.stv("xmat", 0, "xmat_0", 9)
+        G.stv_const("xpos", 0, "xpos_0", 3, _WORLD_DECL)
+        G.stv_const("xquat", 0, "xquat_0", 4, _WORLD_DECL)
+        G.stv_const("xmat", 0, "xmat_0", 9, _WORLD_DECL)
     if not FRAMES_IN_PASS1:
       frame_outputs(i)
     for kind, c in cams.get(i, []):
@@ -917,8 +996,8 @@ def _gen_pos(M: _Model, store_fields=None) -> str:
       E.close()
       G.stv("cinert", 10 * i, f"crb_{i}", 10)
     else:
-      E("double crb_0[10] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};")
-      G.stv("cinert", 0, "crb_0", 10)
+      E(_CRB0_DECL)
+      G.stv_const("cinert", 0, "crb_0", 10, _CRB0_DECL)
     # cdof (mj_comPos :225-268)
     ja, jn = int(m.body_jntadr[i]), int(m.body_jntnum[i])
     for j in range(ja, ja + jn):
@@ -945,11 +1024,19 @@ def _gen_pos(M: _Model, store_fields=None) -> str:
         E(f"mjh::dofComHinge(cdof_{da}, xaxis_{j}, off);")
       E.close()
       for k in range(ndof):
-        G.stv("cdof", 6 * (da + k), f"cdof_{da + k}", 6)
+        cc = const_cdof(m, da + k)
+        if cc is None:
+          G.stv("cdof", 6 * (da + k), f"cdof_{da + k}", 6)
+        else:       # the literals mjh::zero and the 1.0 above leave in cdof_<k>
+          G.stv_const("cdof", 6 * (da + k), f"cdof_{da + k}", 6,
+                      f"const double cdof_{da + k}[6] = {arr_lit(cc)};")
 
   def post2(i):
     # crb_i is final: every child (higher index) has been added, in descending order
-    G.stv("crb", 10 * i, f"crb_{i}", 10)
+    if i:
+      G.stv("crb", 10 * i, f"crb_{i}", 10)
+    else:           # nothing is added to the world's (the parent > 0 test below)
+      G.stv_const("crb", 0, "crb_0", 10, _CRB0_DECL)
     # qM rows of this body's dofs (mj_crb :1370-1399); qM starts zeroed (mju_zero)
     for k in range(M.bdofadr[i], M.bdofadr[i] + M.bdofnum[i]):
       adr = M.Madr[k]
@@ -1124,9 +1211,7 @@ def _gen_va(M: _Model, store_fields=None) -> str:
     G.load("ten_length", "ten_length", m.ntendon)
   E(f"double qfg[{nv}];")
   E(f"mjh::zero(qfg, {nv});")
-  g = np.asarray(m.opt["gravity"], dtype=float)
-  has_gravcomp = bool(m.ngravcomp and not (dsbl & (1 << 5)) and not (dsbl & (1 << 6)) and
-                      np.sqrt(g @ g) != 0)
+  has_gravcomp = M.has_gravcomp
   if has_gravcomp:
     E("// ---- mj_gravcomp (engine_passive.c:381-399), bodies in ascending order")
     for b in range(1, M.nbody):
@@ -1232,8 +1317,11 @@ def _gen_va(M: _Model, store_fields=None) -> str:
   for dof in range(nv):
     G.st("qfrc_spring", dof, f"qfs[{dof}]")
     G.st("qfrc_damper", dof, f"qfd[{dof}]")
-    G.st("qfrc_gravcomp", dof, f"qfg[{dof}]")
-    G.st("qfrc_fluid", dof, "0.0")
+    if has_gravcomp:
+      G.st("qfrc_gravcomp", dof, f"qfg[{dof}]")
+    else:           # mjh::zero's 0.0, never added to
+      G.st_const("qfrc_gravcomp", dof, f"qfg[{dof}]", f"const double qfg[{nv}] = {{0.0}};")
+    G.st_const("qfrc_fluid", dof, "0.0")
     if dsbl & (1 << 5):
       passive = "0.0"
     elif has_gravcomp and dof not in actgc:
@@ -1256,8 +1344,8 @@ def _gen_va(M: _Model, store_fields=None) -> str:
       for c in range(3):
         E(f"keep_stc_{r}[{c}] = P_subtree_com[{3 * r + c}*64];")
     _world_frame(E)
-  E("double cvel_0[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};")
-  G.stv("cvel", 0, "cvel_0", 6)
+  E(_CVEL0_DECL)
+  G.stv_const("cvel", 0, "cvel_0", 6, _CVEL0_DECL)
   _gravity_acc(M, E)
   E("double acca_0[6]; mjh::copy(acca_0, cacc_0, 6);")
   E(f"double qacc[{nv}];")
@@ -1358,7 +1446,11 @@ def _gen_va(M: _Model, store_fields=None) -> str:
         j += 1
     G.stv("cvel", 6 * i, f"cvel_{i}", 6)
     for k in range(bda, bda + dn):
-      G.stv("cdof_dot", 6 * k, f"cdofdot_{k}", 6)
+      if const_cdof(m, k) is None:
+        G.stv("cdof_dot", 6 * k, f"cdofdot_{k}", 6)
+      else:         # a free joint's translational rows: the zeros declared above
+        G.stv_const("cdof_dot", 6 * k, f"cdofdot_{k}", 6,
+                    f"double cdofdot_{k}[6] = {{0.0, 0.0, 0.0, 0.0, 0.0, 0.0}};")
     # forward step of both recursions (engine_core_smooth.c:1986-2006)
     E(f"double cacc_{i}[6], cfrc_{i}[6], acca_{i}[6], frca_{i}[6];")
     E.open()
@@ -1399,7 +1491,7 @@ def _gen_va(M: _Model, store_fields=None) -> str:
           E("qfi = cflag ? qfi : qfa;")
         else:
           E("qfi = qfa;")
-        G.st("qfrc_constraint", k, "0.0")
+        G.st_const("qfrc_constraint", k, "0.0")
         G.st("qfrc_inverse", k, "qfi")
         E(f"qo_lds[{_ll('va')[0]}*{nv} + {k}] = qfi;")
       E.close()
@@ -1522,7 +1614,7 @@ def _gen_acc(M: _Model, store_fields=None) -> str:
       else:
         E(f"const double qfa = qfi + ({lit(m.dof_armature[k])} * qacc[{k}] - qfp_{k} - 0.0);")
         E("qfi = cflag ? qfi : qfa;" if M.cmode == "list" else "qfi = qfa;")
-        G.st("qfrc_constraint", k, "0.0")
+        G.st_const("qfrc_constraint", k, "0.0")
         G.st("qfrc_inverse", k, "qfi")
         E(f"qo_lds[{_ll('va')[0]}*{nv} + {k}] = qfi;")
       E.close()
@@ -1619,8 +1711,11 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
              va_slots=None) -> str:
   """HIP source of the four stage kernels of model `m` (skipstage = mjSTAGE_NONE).
 
-  Also emits `fast_body_<name>`, which runs the four stage bodies for one instance in
-  order (the host harness's entry), and `launch_fast_<name>`, which launches the kernels.
+  Also emits `fast_body_<name>`, which runs fast_const_<name> and then the stage bodies for
+  one instance in order (the host harness's entry), `launch_fast_<name>`, which launches the
+  kernels, and with CONST_ONCE `k_const_<name>` / `launch_const_<name>` /
+  `const_stores_<name>` (a run-time code object: `k_const_<name>` and the device global
+  `k_const_count_<name>`, both with C linkage, whether the switch is on or not).
   store_fields: optional set of mirror fields to store (default: all); used only by
   performance experiments (tools/exp_bounds.py) to separate compute from store costs.
   shared: the launch functions get external linkage (a model compiled in another
@@ -1666,9 +1761,26 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
                             b)
                    if st in NT_LOAD_SV_STAGES and st not in NT_LOAD_STAGES else b)
               for st, b in bodies.items()}
+  # the generator-constant stores (CONST_ONCE): every lane of every block of the capacity, so
+  # no instance bound; plain stores (one launch per context, nothing to keep out of L2)
+  nconst = len(M.consts)
+  const_text = ""
+  if CONST_ONCE:
+    C = _Stage(M)
+    C.pointers(sorted({f for f, _ in M.consts}))
+    for d in M.const_decls:
+      for line in d.split("\n"):
+        C.E(line)
+    for (f, k), expr in M.consts.items():
+      C.E(f"P_{f}[{k}*64] = {expr};")
+    C.E("(void)mr; (void)blk; (void)lane;")
+    const_text = C.E.text()
   if M.cmode in ("none", "list") and store_fields is None:
-    elided = fd_elided(bodies.values())
+    # the host entry's FD blocks keep the elided fields untouched, constants included (on the
+    # device k_const runs the plain instantiation over the whole capacity)
+    elided = fd_elided(list(bodies.values()) + [const_text])
     bodies = {st: _elide_stores(b, elided) for st, b in bodies.items()}
+    const_text = _elide_stores(const_text, elided)
   out = [f"// GENERATED by mujoco_inversedynamicstest_amd/codegen.py -- do not edit.",
          f"// model '{name}' (nq={m.nq} nv={m.nv} nbody={m.nbody}), hash {model_hash(m)}"]
   exact = exact_fp(m)
@@ -1679,6 +1791,13 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
     out.append(f"template <bool SV = true, bool FD = false>\n"
                f"MJH_HD void fast_{st}_{name}(const Mirror& mr, int blk, int lane, int B, "
                f"{params}) {{\n{bodies[st]}\n}}\n")
+  const_call = ""
+  if CONST_ONCE:
+    out.append(f"template <bool FD = false>\n"
+               f"MJH_HD void fast_const_{name}(const Mirror& mr, int blk, int lane) {{\n"
+               f"{const_text}\n}}\n")
+    const_call = (f"  if (fd) fast_const_{name}<true>(mr, blk, lane);\n"
+                  f"  else fast_const_{name}<false>(mr, blk, lane);\n")
   out.append(f"""MJH_HD void fast_body_{name}(
     const Mirror& mr, int blk, int lane, int B, const double* __restrict__ qpos_in,
     const double* __restrict__ qvel_in, const double* __restrict__ qacc_in,
@@ -1689,7 +1808,7 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
   double qo_lds[{64 * max(M.nv, 1)}];             // LDS on the device (k_va)
   double qmr[{max(1, m.nM)}];                        // registers on the device (k_all)
   const bool fd = mr.fd_elide && blk >= mr.full_blk;   // mjd_inverseFD's perturbed blocks
-""" + "".join(f"  if (fd) fast_{st}_{name}<true, true>(mr, blk, lane, B, {_SIG[st][1]});\n"
+""" + const_call + "".join(f"  if (fd) fast_{st}_{name}<true, true>(mr, blk, lane, B, {_SIG[st][1]});\n"
               f"  else fast_{st}_{name}<true, false>(mr, blk, lane, B, {_SIG[st][1]});\n"
               for st in STAGES)
              + (f"""  if (qfrc_out && (long)blk*64 + lane < B) {{
@@ -2079,6 +2198,22 @@ __global__ __launch_bounds__(64, 1) void k_acc_{name}(Mirror mr, int B,
                        status, efc_count);
   }}
 }}""")
+  # k_const: one lane per instance slot of the whole capacity (nblk blocks of 64), launched by
+  # the library when the context's constant slots may be stale (mjhip.hip ensure_const). A
+  # run-time code object always has one, and its count as a device global, both found by name
+  if CONST_ONCE or extern_c:
+    kbody = f"  fast_const_{name}(mr, blockIdx.x, threadIdx.x);" if CONST_ONCE else "  (void)mr;"
+    out.append(f"{linkage}__global__ __launch_bounds__(64) void k_const_{name}(Mirror mr) {{\n"
+               f"{kbody}\n}}")
+    if extern_c:
+      out.append(f'extern "C" __device__ __attribute__((used)) int k_const_count_{name} = '
+                 f"{nconst};")
+    else:
+      out.append(f"""{"" if shared else "static "}void launch_const_{name}(hipStream_t s, const Mirror& mr, int nblk) {{
+  hipLaunchKernelGGL(k_const_{name}, dim3(nblk), dim3(64), 0, s, mr);
+}}
+{"" if shared else "static "}int const_stores_{name}() {{ return {nconst}; }}""")
+  assert len(M.consts) == nconst, "a constant store emitted after fast_const was written"
   out.append(f"""{"" if shared else "static "}void launch_fast_{name}(dim3 g, dim3 b, hipStream_t s, const Mirror& mr,
     int B, const double* qpos_in, const double* qvel_in, const double* qacc_in, double* qfrc_out,
     int* status, int* worklist, int* worklist_count, int* worklist_next, int* efc_count,
@@ -2115,6 +2250,16 @@ __global__ __launch_bounds__(64, 1) void k_acc_{name}(Mirror mr, int B,
   if exact:
     out.append("#if defined(__clang__)\n#pragma clang fp contract(fast)\n#endif")
   return "\n".join(out) + "\n"
+
+
+def const_slots(m, va_slots=None) -> list:
+  """The (field, index) mirror slots whose stores CONST_ONCE moves from the stage bodies of
+  model m into fast_const_<name>, in emission order (empty with the switch off): what
+  mjhip_contextConstStores counts."""
+  M = _Model(m, va_slots)
+  for st in STAGES:
+    _GEN[st](M, None)
+  return list(M.consts)
 
 
 _TOKEN = re.compile(r'"(?:\\.|[^"\\\n])*"|\'(?:\\.|[^\'\\\n])*\'|//[^\n]*|/\*.*?\*/|\s+',
@@ -2187,6 +2332,9 @@ def generate_registries(entries) -> tuple:
       main.append(f"void launch_skip_{name}(hipStream_t, const Mirror&, int, int, double*, "
                   "int*, int*);")
       main.append(f"int lds_fast_{name}();")
+      if CONST_ONCE:
+        main.append(f"void launch_const_{name}(hipStream_t, const Mirror&, int);")
+        main.append(f"int const_stores_{name}();")
       if constraint_mode(m) == "all":
         main.append(f"void launch_split_{name}(hipStream_t, const Mirror&, int, int, "
                     "const double*, const double*, const double*, int*, int*, int*);")
@@ -2198,12 +2346,14 @@ def generate_registries(entries) -> tuple:
     fns = ", ".join(f"launch_{k}_{name}" if vaskip else "nullptr" for k in ("vaskip", "fdskip"))
     split = f"launch_split_{name}" if constraint_mode(m) == "all" else "nullptr"
     fdall = f"launch_fdall_{name}" if fdall_ok(m) else "nullptr"
+    const = f"launch_const_{name}, const_stores_{name}" if CONST_ONCE else "nullptr, nullptr"
     reg.append(f'  {{0x{fields.model_signature(m):016x}ull, launch_fast_{name}, "{name}", '
                f'{CONSTRAINT_MODES[constraint_mode(m)]}, {fns}, launch_skip_{name}, {split}, '
-               f'{fdall}, lds_fast_{name}}},')
+               f'{fdall}, lds_fast_{name}, {const}}},')
   main.append("static const FastKernelEntry g_fast_kernels[] = {")
   main.extend(reg)
-  main.append("  {0ull, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}};")
+  main.append("  {0ull, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, "
+              "nullptr, nullptr}};")
   return "\n".join(main) + "\n", "\n".join(exact) + "\n"
 
 
@@ -2218,10 +2368,12 @@ def generate_registry(entries) -> str:
     fns = ", ".join(f"launch_{k}_{name}" if sk else "nullptr" for k in ("vaskip", "fdskip"))
     split = f"launch_split_{name}" if constraint_mode(m) == "all" else "nullptr"
     fdall = f"launch_fdall_{name}" if fdall_ok(m) else "nullptr"
+    const = f"launch_const_{name}, const_stores_{name}" if CONST_ONCE else "nullptr, nullptr"
     reg.append(f'  {{0x{fields.model_signature(m):016x}ull, launch_fast_{name}, "{name}", '
                f'{CONSTRAINT_MODES[constraint_mode(m)]}, {fns}, launch_skip_{name}, {split}, '
-               f'{fdall}, lds_fast_{name}}},')
+               f'{fdall}, lds_fast_{name}, {const}}},')
   out.append("static const FastKernelEntry g_fast_kernels[] = {")
   out.extend(reg)
-  out.append("  {0ull, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}};")
+  out.append("  {0ull, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, "
+             "nullptr, nullptr}};")
   return "\n".join(out) + "\n"

@@ -44,6 +44,14 @@ struct FastKernelEntry {
   // static LDS in bytes of the compiled k_all variants (hipFuncGetAttributes), -1 on a HIP
   // error; null for run-time kernels, whose code object mjhip_contextLoadKernel queries
   int (*lds_bytes)();
+  // k_const (codegen.py CONST_ONCE): stores the model-constant output slots the stage bodies
+  // leave out, over all nblk 64-instance blocks of the capacity; the library runs it before
+  // the first generated-kernel launch of a context and again after anything that may have
+  // overwritten the slots (mjhip.hip ensure_const). const_stores: their count per instance.
+  // Both null when the kernels store everything themselves; a run-time kernel's are found in
+  // its code object (mjhip_contextLoadKernel)
+  void (*launch_const)(hipStream_t, const Mirror&, int);
+  int (*const_stores)();
 };
 
 // static LDS a k_all workgroup may hold while four of them share a CU's 160 KB

@@ -507,6 +507,13 @@ struct mjhipContext_ {
   FastKernelEntry rt{};
   std::string rt_name;
   hipDeviceptr_t rt_tbuf = nullptr;        // the code object's mjh_tbuf (null: none)
+  hipFunction_t rt_const_fn = nullptr;     // the code object's k_const_<name>
+  int rt_nconst = 0;                       // and its k_const_count_<name>
+  // the model-constant output slots the generated stage bodies leave to k_const may not hold
+  // their values: set at creation, by mjhip_contextLoadKernel (another code object carries its
+  // own constants) and by every mjhip_mirrorUpload; cleared by ensure_const
+  bool const_stale = true;
+  int const_launches = 0;                  // k_const launches so far (mjhip_contextConstLaunches)
   // per-stage timers (mjhip_contextTimers): the device accumulator the phase marks add to,
   // the reference's mjTimerStat table, and the events around each timed call
   unsigned long long* tbuf = nullptr;
@@ -765,6 +772,9 @@ MJHIP_API int mjhip_contextCreateCapped(const mjhipModel* m, int device, int cap
     return MJHIP_ERR_HIP;
   }
   hipMemset(c->mirror_buf, 0, mb);
+  // the context's stream does not wait for the null stream: the zero fill is complete before
+  // anything on it (k_const, the first launch's stores) touches the mirror
+  hipStreamSynchronize(nullptr);
   char* p = (char*)c->mirror_buf;
 #define XD(name, d0, d1, stage) c->mirror.name = (double*)p; \
   c->fields[#name] = {c->mirror.name, c->mirror.name##_n}; \
@@ -998,10 +1008,32 @@ MJHIP_API int mjhip_contextLoadKernel(mjhipContext* c, const void* image, size_t
               "four workgroups share a CU", kname.c_str(), lds, kFastLdsBudget);
     return MJHIP_ERR_MODEL;
   }
+  // its constant stores: the kernel and their count, both by name (the stage bodies of such
+  // an object leave those slots to it, so one without it would leave them unwritten)
+  hipFunction_t cfn = nullptr;
+  hipDeviceptr_t ncp = nullptr;
+  size_t ncbytes = 0;
+  int nconst = 0;
+  const std::string cname = std::string("k_const_") + name;
+  const std::string nname = std::string("k_const_count_") + name;
+  if (hipModuleGetFunction(&cfn, mod, cname.c_str()) != hipSuccess ||
+      hipModuleGetGlobal(&ncp, &ncbytes, mod, nname.c_str()) != hipSuccess ||
+      ncbytes != sizeof(int) ||
+      hipMemcpy(&nconst, (const void*)ncp, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess ||
+      nconst < 0) {
+    (void)hipGetLastError();
+    hipModuleUnload(mod);
+    set_error("mjhip_contextLoadKernel: no kernel '%s' (or its count '%s') in the code object",
+              cname.c_str(), nname.c_str());
+    return MJHIP_ERR_MODEL;
+  }
   c->fast_lds = lds;
   if (c->rt_module) hipModuleUnload(c->rt_module);
   c->rt_module = mod;
   c->rt_fn = fn;
+  c->rt_const_fn = cfn;
+  c->rt_nconst = nconst;
+  c->const_stale = true;
   size_t tbytes = 0;                       // its per-stage timer pointer (MJH_TBUF_EXTERN)
   if (hipModuleGetGlobal(&c->rt_tbuf, &tbytes, mod, "mjh_tbuf") != hipSuccess ||
       tbytes != sizeof(void*)) {
@@ -1110,6 +1142,38 @@ MJHIP_API int mjhip_contextFastKernelLds(const mjhipContext* c) {
 
 MJHIP_API int mjhip_contextLastPath(const mjhipContext* c) { return c ? c->last_path : -1; }
 
+MJHIP_API int mjhip_contextConstStores(const mjhipContext* c) {
+  if (!c || !c->fast) return 0;
+  if (c->fast == &c->rt) return c->rt_nconst;
+  return c->fast->const_stores ? c->fast->const_stores() : 0;
+}
+
+MJHIP_API int mjhip_contextConstLaunches(const mjhipContext* c) {
+  return c ? c->const_launches : 0;
+}
+
+// Before any launch that runs generated stage bodies: the model-constant slots they leave out
+// (codegen.py CONST_ONCE) are written by k_const over the whole capacity when they may be
+// stale, on the context's current stream, so ahead of the launch that follows. The generic
+// kernel stores the same values in the same slots, so the two paths mix freely on a context.
+static int ensure_const(mjhipContext* c) {
+  if (!c->const_stale || !c->fast) return MJHIP_OK;
+  if (mjhip_contextConstStores(c) > 0) {
+    const int nblk = c->capacity / 64;
+    if (c->fast == &c->rt) {
+      void* args[] = {&c->mirror};
+      HIPCHECK(hipModuleLaunchKernel(c->rt_const_fn, nblk, 1, 1, 64, 1, 1, 0, c->stream, args,
+                                     nullptr));
+    } else {
+      c->fast->launch_const(c->stream, c->mirror, nblk);
+      HIPCHECK(hipGetLastError());
+    }
+    c->const_launches++;
+  }
+  c->const_stale = false;
+  return MJHIP_OK;
+}
+
 MJHIP_API const char* mjhip_contextConstraintKernel(const mjhipContext* c) {
   return c ? c->con_kernel : nullptr;
 }
@@ -1203,6 +1267,7 @@ static int launch_inverse(mjhipContext* c, int B, const double* qpos, const doub
   c->last_path = 0;
   if (skipstage == mjhipSTAGE_NONE && c->fast && !(flags & MJHIP_FLAG_GENERIC)) {
     c->last_path = 1;
+    if (const int rc = ensure_const(c)) return rc;
     // two work-list counters alternate: this launch counts into `cnt` (zeroed by the
     // previous launch's k_pos, or at context creation) and zeroes `nxt` for the next one
     int* cnt = c->worklist + c->wl_parity;
@@ -1350,6 +1415,7 @@ static int launch_inverse(mjhipContext* c, int B, const double* qpos, const doub
                          qacc, c->mirror.qacc, B, nv);
     }
     c->last_path = 2;
+    if (const int rc = ensure_const(c)) return rc;
     c->fast->launch_skip(c->stream, c->mirror, B, skipstage, qfrc, status, c->mirror.efc_count);
     HIPCHECK(hipGetLastError());
     if (c->fast->cmode) {                // work-list rows, or every instance (contacts)
@@ -1797,6 +1863,7 @@ MJHIP_API int mjhip_mirrorUpload(mjhipContext* c, const char* field, int first, 
     blockIndex(inst - b0*64, S, ct, &base, &step);
     for (int k = 0; k < S; k++) tmp[base + (size_t)k*step] = src[(size_t)i*S + k];
   }
+  c->const_stale = true;                 // the rows may cover slots only k_const writes
   HIPCHECK(hipMemcpyAsync(p + (size_t)b0*S*64, tmp.data(), tmp.size()*sizeof(double),
                           hipMemcpyHostToDevice, c->stream));
   HIPCHECK(hipStreamSynchronize(c->stream));
@@ -1947,6 +2014,8 @@ MJHIP_API int mjhip_inverseFDBatchEx(mjhipContext* c, int B, const mjtNum* qpos,
   if (layout) {
     c->mirror.fd_elide = 1;
     c->mirror.full_blk = (B + 63) / 64;
+    // k_fdall, k_vaskip and k_fdskip run generated stage bodies too
+    if (const int rc2 = ensure_const(c)) return rc2;
   }
   // with a skip layout only the position-stage block is expanded: the skip kernels read their
   // centre's inputs and perturb them in registers (the fall-back expands the rest, below)

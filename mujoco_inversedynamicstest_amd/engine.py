@@ -57,6 +57,8 @@ SIGNATURES = {
                                                ctypes.c_ulonglong, ctypes.c_int]),
     "mjhip_worklistCount": (ctypes.c_int, [_V]),
     "mjhip_contextLastPath": (ctypes.c_int, [_V]),
+    "mjhip_contextConstStores": (ctypes.c_int, [_V]),
+    "mjhip_contextConstLaunches": (ctypes.c_int, [_V]),
     "mjhip_contextConstraintKernel": (ctypes.c_char_p, [_V]),
     "mjhip_contextStream": (_V, [_V]),
     "mjhip_contextSetStream": (ctypes.c_int, [_V, _V]),
@@ -269,6 +271,17 @@ class InverseEngine:
     straight-line mj_inverseSkip(POS / VEL) kernels, 3 the straight-line pipeline of a contact
     model split over two streams."""
     return lib().mjhip_contextLastPath(self.ctx)
+
+  @property
+  def const_stores(self):
+    """Model-constant output slots per instance that the straight-line kernel leaves to its
+    once-per-context k_const (0: it stores everything itself, or the generic kernel runs)."""
+    return lib().mjhip_contextConstStores(self.ctx)
+
+  @property
+  def const_launches(self):
+    """k_const launches of this context so far."""
+    return lib().mjhip_contextConstLaunches(self.ctx)
 
   def worklist_count(self):
     return lib().mjhip_worklistCount(self.ctx)

@@ -52,12 +52,17 @@ def main(src, dst, config=2, batch=65536):
     kernels = [k for k in kernels if "contact" in k or k.startswith("k_constraint")]
   else:
     kernels = [k for k in kernels if "contact" not in k]
+  # k_const_<model> runs once per context (codegen.CONST_ONCE), not once per launch: listed
+  # apart, over the context's capacity, and left out of the per-launch traffic
+  once = {k: {"fetch_bytes": fetch[k] * calib, "write_bytes": write.get(k, 0.0)}
+          for k in kernels if k.startswith("k_const_")}
+  kernels = [k for k in kernels if k not in once]
   rows = {k: {"fetch_bytes": fetch[k] * calib, "write_bytes": write.get(k, 0.0)} for k in kernels}
   total = sum(v["fetch_bytes"] + v["write_bytes"] for v in rows.values())
   from mujoco_inversedynamicstest_amd import codegen
   out = {"batch": B, "model": name, "config": config, "fetch_correction": calib,
          "source_sha": codegen.source_hash(m, name),
-         "kernels": rows, "traffic_bytes_per_launch": total,
+         "kernels": rows, "once_per_context": once, "traffic_bytes_per_launch": total,
          "traffic_bytes_per_eval": total / B,
          "note": "FETCH_SIZE x correction (calibrated on k_fac reading exactly qM) + WRITE_SIZE, "
                  "averaged over the dispatches of tools/pmc.sh"}
