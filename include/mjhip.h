@@ -253,6 +253,13 @@ typedef struct mjhipData_ {
 #define XJ(type, name, dim) type* name;
   MJHIP_DATA_SPARSE
 #undef XJ
+  /* activation state of stateful actuators (MJHIP_DATA_ACTIVATION): act (na) is read by the
+   * calls that run mj_fwdActuation (mjhip_inverseFD with flg_actuation) or mjd_actuator_vel
+   * (mjENBL_INVDISCRETE with the implicit integrators); such a call on a model with na > 0
+   * and act == NULL reports through the error callback. act_dot / act_next may be NULL. */
+#define XD(name, d0, d1, stage) mjtNum* name;
+  MJHIP_DATA_ACTIVATION
+#undef XD
 } mjhipData;
 
 /*---------------------------- status codes of the batch API ------------------------------*/
@@ -384,9 +391,34 @@ MJHIP_API int mjhip_inverseBatch(mjhipContext* c, int B,
  * MJHIP_INST_UNSUPPORTED (its qacc is qacc_smooth). qpos/qvel (B x nq, B x nv) and optional
  * ctrl (B x nu) are row-major inputs unless MJHIP_FLAG_MIRROR_INPUT; qfrc_applied and
  * xfrc_applied are read from the mirror (mjhip_mirrorUpload; zero after context creation).
- * Optional qacc (B x nv) receives the result; every mjData field is in the mirror. */
+ * Optional qacc (B x nv) receives the result; every mjData field is in the mirror.
+ * Models with activation dynamics or muscle gain/bias are MJHIP_ERR_MODEL here: they go
+ * through mjhip_forwardBatchEx, which takes the activations. */
 MJHIP_API int mjhip_forwardBatch(mjhipContext* c, int B, const mjtNum* qpos, const mjtNum* qvel,
                                  const mjtNum* ctrl, mjtNum* qacc, int flags, int* status);
+
+/* mjhip_forwardBatch with the activation state: act (B x na, row-major; NULL: the mirror's
+ * act, zero after context creation as in mj_resetData, set with mjhip_mirrorUpload("act"))
+ * is the input of mj_fwdActuation (engine_forward.c:276-515) for actuators with dyntype
+ * integrator, filter, filterexact or muscle and for muscle gain / bias. Optional act_dot and
+ * act_next (B x na) receive d->act_dot and the activation mj_advance would integrate to
+ * (nextActivation :236-259, :738-750); act itself is not changed. User dynamics, gain and
+ * bias are MJHIP_ERR_MODEL. */
+MJHIP_API int mjhip_forwardBatchEx(mjhipContext* c, int B, const mjtNum* qpos,
+                                   const mjtNum* qvel, const mjtNum* ctrl, const mjtNum* act,
+                                   mjtNum* qacc, mjtNum* act_dot, mjtNum* act_next, int flags,
+                                   int* status);
+
+/* Batched mj_fwdActuation alone, over the actuator_length, actuator_velocity and
+ * actuator_moment the context's last call left in the mirror (the call a muscle-driven
+ * inverse-dynamics user makes after mjhip_inverseBatch: qfrc_inverse - qfrc_actuator is what
+ * the muscles do not explain). ctrl (B x nu) and act (B x na) may be NULL: the mirror's values
+ * are used. Optional outputs act_dot, act_next (B x na) and qfrc_actuator (B x nv), row-major,
+ * host arrays or device arrays with MJHIP_FLAG_DEVICE_PTRS; actuator_force, act_dot, act_next
+ * and qfrc_actuator are in the mirror afterwards. status (B ints, host) may be NULL. */
+MJHIP_API int mjhip_actuationBatch(mjhipContext* c, int B, const mjtNum* ctrl,
+                                   const mjtNum* act, mjtNum* act_dot, mjtNum* act_next,
+                                   mjtNum* qfrc_actuator, int flags, int* status);
 
 /* copy one mirror field (reference name) of instances [first, first+count) to/from host
  * memory in the reference's per-instance row-major layout (count x fieldSize) */
@@ -426,12 +458,22 @@ MJHIP_API int mjhip_inverseFDBatch(mjhipContext* c, int B,
 /* mjhip_inverseFDBatch with the reference's flg_actuation (engine_derivative_fd.c:160-168):
  * when set, every evaluation's force is qfrc_inverse - qfrc_actuator (mj_fwdActuation of the
  * base state's controls `ctrl`, B x nu, which may be NULL when nu == 0). Actuators with
- * activation dynamics or muscle/user gain and bias are MJHIP_ERR_MODEL. */
+ * activation dynamics or muscle/user gain and bias are MJHIP_ERR_MODEL here (their
+ * activations are an input: mjhip_inverseFDBatchAct). */
 MJHIP_API int mjhip_inverseFDBatchEx(mjhipContext* c, int B, const mjtNum* qpos,
                                      const mjtNum* qvel, const mjtNum* qacc, const mjtNum* ctrl,
                                      mjtNum eps, int flg_actuation, mjtNum* DfDq, mjtNum* DfDv,
                                      mjtNum* DfDa, mjtNum* DsDq, mjtNum* DsDv, mjtNum* DsDa,
                                      mjtNum* DmDq, int flags);
+
+/* mjhip_inverseFDBatchEx with the base states' activations `act` (B x na; may be NULL when
+ * na == 0 or flg_actuation == 0): every perturbed instance gets its base state's act as it
+ * gets its ctrl, so flg_actuation serves actuators with activation dynamics and muscles. */
+MJHIP_API int mjhip_inverseFDBatchAct(mjhipContext* c, int B, const mjtNum* qpos,
+                                      const mjtNum* qvel, const mjtNum* qacc, const mjtNum* ctrl,
+                                      const mjtNum* act, mjtNum eps, int flg_actuation,
+                                      mjtNum* DfDq, mjtNum* DfDv, mjtNum* DfDa, mjtNum* DsDq,
+                                      mjtNum* DsDv, mjtNum* DsDa, mjtNum* DmDq, int flags);
 
 /* Per-instance row capacities of a model on the device path: constraint rows (efc) and
  * contacts an instance can produce (exact upper bounds for the implemented functions). Size
@@ -522,7 +564,9 @@ MJHIP_API void mjhip_xfrcAccumulate(const mjhipModel* m, mjhipData* d, mjtNum* q
  * J'xfrc_applied - qfrc_inverse|); qfrc_constraint and efc_force keep the forward values */
 MJHIP_API void mjhip_compareFwdInv(const mjhipModel* m, mjhipData* d);
 /* mjd_inverseFD (engine_derivative_fd.c:611-719) for one mjData; d keeps its qpos/qvel/qacc
- * and holds the outputs of the reference's last evaluation afterwards */
+ * and holds the outputs of the reference's last evaluation afterwards. d->act is passed to
+ * every evaluation (mjhip_inverseFDBatchAct); with na > 0 it must not be NULL when
+ * flg_actuation is set or the model's implicit mj_discreteAcc reads it. */
 MJHIP_API void mjhip_inverseFD(const mjhipModel* m, mjhipData* d, mjtNum eps,
                                mjtByte flg_actuation, mjtNum* DfDq, mjtNum* DfDv, mjtNum* DfDa,
                                mjtNum* DsDq, mjtNum* DsDv, mjtNum* DsDa, mjtNum* DmDq);

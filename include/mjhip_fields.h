@@ -266,9 +266,23 @@
   X(int,     D_colind,             nD,        1) \
   X(int,     mapM2D,               nD,        1)
 
+/* mjModel arrays of the activation state and of muscles (mjxmacro.h MJMODEL_POINTERS), after
+ * every older pointer of mjhipModel, so that the struct a caller compiled against an earlier
+ * header passes is a prefix of this one. The library reads them only for a model that has
+ * activations or a muscle gain / bias (mjhip_modelUsesActivation); for any other model their
+ * values follow from the rest (actadr -1, actnum 0, nothing limited or early). */
+#define MJHIP_MODEL_POINTERS_A \
+  X(int,     actuator_actadr,      nu,        1) \
+  X(int,     actuator_actnum,      nu,        1) \
+  X(mjtByte, actuator_actlimited,  nu,        1) \
+  X(mjtByte, actuator_actearly,    nu,        1) \
+  X(mjtNum,  actuator_actrange,    nu,        2) \
+  X(mjtNum,  actuator_lengthrange, nu,        2)
+
 #define MJHIP_MODEL_POINTERS \
   MJHIP_MODEL_POINTERS_M      \
-  MJHIP_MODEL_POINTERS_D
+  MJHIP_MODEL_POINTERS_D      \
+  MJHIP_MODEL_POINTERS_A
 
 /* Per-instance fp64 mjData fields produced or consumed by mj_inverseSkip, in pipeline order.
  * XD(name, dim0, dim1, stage): stage 0 = input, 1 = position, 2 = velocity, 3 = acceleration.
@@ -345,6 +359,18 @@
   XD(qfrc_actuator,     nv,      1,   5) \
   XD(qfrc_smooth,       nv,      1,   5) \
   XD(qacc_smooth,       nv,      1,   5)
+
+/* Activation state of stateful actuators (mjData act / act_dot, mjxmacro.h MJDATA_POINTERS;
+ * mj_fwdActuation engine_forward.c:276-515): act is an input (stage 4), act_dot an output of
+ * mj_fwdActuation (stage 5). act_next is the activation mj_advance's loop (:738-750) would
+ * integrate to, nextActivation(act, act_dot) (:236-259); the reference keeps it in no field
+ * (it overwrites act), here mj_fwdActuation stores it beside act_dot and act stays an input.
+ * A list of its own, appended after every other field of mjhipData, Lane and the mirror:
+ * MJHIP_DATA_FORWARD is expanded by hand in places that must not change. */
+#define MJHIP_DATA_ACTIVATION \
+  XD(act,               na,      1,   4) \
+  XD(act_dot,           na,      1,   5) \
+  XD(act_next,          na,      1,   5)
 
 /* mjData fields the sensor stages compute on demand (stage 6): mj_subtreeVel
  * (engine_core_smooth.c:1900-1958) for subtreelinvel/subtreeangmom sensors and

@@ -26,8 +26,8 @@
  * (:2083-2104, mju_superSparse engine_util_sparse.c:520-550, restated below).
  *
  * Models are checked for features the device path does not implement and which mjhipModel
- * does not carry (flexes, plugins, muscle/user actuator gains and biases, an affine velocity
- * gain with activation dynamics, SDF geoms; adapter_unsupported): such a model is an
+ * does not carry (flexes, plugins, user actuator gains and biases, SDF geoms;
+ * adapter_unsupported): such a model is an
  * mju_error, never a silently different result. Predefined <contact><pair>s are carried.
  *
  * Build (in the reference tree): drop engine_inverse.c from src/engine/CMakeLists.txt,
@@ -51,13 +51,8 @@ static const char* adapter_unsupported(const mjModel* m) {
   if (m->nflex) return "flexes";
   if (m->nplugin) return "plugins";
   for (int i = 0; i < m->nu; i++) {
-    /* mjd_actuator_vel reads mjData.act for these (engine_derivative.c:855-863) */
-    if (m->actuator_dyntype[i] != mjDYN_NONE && m->actuator_gaintype[i] == mjGAIN_AFFINE &&
-        m->actuator_gainprm[mjNGAIN*i + 2] != 0) {
-      return "an affine velocity gain with activation dynamics";
-    }
-    if (m->actuator_gaintype[i] >= mjGAIN_MUSCLE || m->actuator_biastype[i] >= mjBIAS_MUSCLE) {
-      return "muscle or user actuator gain/bias";
+    if (m->actuator_gaintype[i] >= mjGAIN_USER || m->actuator_biastype[i] >= mjBIAS_USER) {
+      return "user actuator gain/bias";
     }
   }
   for (int i = 0; i < m->ngeom; i++) {
@@ -97,6 +92,7 @@ static void model_view(const mjModel* m, const mjData* d, mjhipModel* hm) {
   /* arrays that live in mjModel */
 #define X(type, name, d0, d1) hm->name = m->name;
   MJHIP_MODEL_POINTERS_M
+  MJHIP_MODEL_POINTERS_A
 #undef X
   /* model-constant sparse structures that live in mjData in the reference */
 #define X(type, name, d0, d1) hm->name = d->name;
@@ -141,6 +137,11 @@ static void data_fields(mjData* d, mjhipData* hd) {
   MJHIP_DATA_FORWARD
   MJHIP_DATA_SENSOR_AUX
 #undef XD
+  /* the activation state: mjd_actuator_vel (mjENBL_INVDISCRETE, implicit integrators) and
+   * mjd_inverseFD's flg_actuation read act; act_dot is mj_fwdActuation's output. mjData has
+   * no act_next (mj_advance writes it over act), so that pointer stays NULL. */
+  hd->act = d->act;
+  hd->act_dot = d->act_dot;
   /* the tendon Jacobian's compressed structure (used by sparse-mode models) */
   hd->ten_J_rownnz = d->ten_J_rownnz;
   hd->ten_J_rowadr = d->ten_J_rowadr;

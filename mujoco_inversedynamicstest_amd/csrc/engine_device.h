@@ -460,6 +460,11 @@ struct Lane {
   // with lanes that are elsewhere in their iterations
   double* ccdx;
   int* ccdxi;
+  // activation state (MJHIP_DATA_ACTIVATION): act in, act_dot / act_next out; null pointers
+  // in a harness that binds no activations (only models with na == 0 run there)
+#define XD(name, d0, d1, stage) SP<S> name;
+  MJHIP_DATA_ACTIVATION
+#undef XD
 };
 
 // chain[k] for body k (the fused path's ancestor test, one bit per body)
@@ -7730,6 +7735,147 @@ MJH_HD void mulM(const mjhipModel& m, const Lane<S>& d, SP<S> res, SP<S> vec) {
   }
 }
 
+//---------------------------------- actuator models (engine_util_misc.c) --------------------
+
+// mjMAX (mjmacro.h): the first argument unless the second is greater
+MJH_HD double max2(double a, double b) { return a > b ? a : b; }
+
+// mju_sigmoid engine_util_misc.c:1470-1483: quintic over 0 <= x <= 1
+MJH_HD double sigmoid(double x) {
+  if (x <= 0) return 0;
+  if (x >= 1) return 1;
+  return x*x*x * (3*x * (2*x - 5) + 10);
+}
+
+// mju_muscleGainLength engine_util_misc.c:503-525
+MJH_HD double muscleGainLength(double length, double lmin, double lmax) {
+  if (lmin <= length && length <= lmax) {
+    const double a = 0.5*(lmin+1);         // mid-ranges (maximum is at 1.0)
+    const double b = 0.5*(1+lmax);
+    if (length <= a) {
+      const double x = (length-lmin) / max2(MINVAL, a-lmin);
+      return 0.5*x*x;
+    } else if (length <= 1) {
+      const double x = (1-length) / max2(MINVAL, 1-a);
+      return 1 - 0.5*x*x;
+    } else if (length <= b) {
+      const double x = (length-1) / max2(MINVAL, b-1);
+      return 1 - 0.5*x*x;
+    } else {
+      const double x = (lmax-length) / max2(MINVAL, lmax-b);
+      return 0.5*x*x;
+    }
+  }
+  return 0.0;
+}
+
+// the normalized length L, normalized velocity V, peak force and velocity scale L0*vmax that
+// mju_muscleGain, mju_muscleBias and mjd_muscleGain_vel derive alike from
+// prm = (range[2], force, scale, lmin, lmax, vmax, fpmax, fvmax)
+struct MuscleNorm {
+  double force, L, V, L0vmax;
+};
+MJH_HD MuscleNorm muscleNorm(double len, double vel, const double lengthrange[2], double acc0,
+                             const double* prm) {
+  MuscleNorm r;
+  r.force = prm[2];
+  if (r.force < 0) r.force = prm[3] / max2(MINVAL, acc0);     // scale force if negative
+  const double L0 = (lengthrange[1]-lengthrange[0]) / max2(MINVAL, prm[1]-prm[0]);
+  r.L = prm[0] + (len-lengthrange[0]) / max2(MINVAL, L0);
+  r.L0vmax = max2(MINVAL, L0*prm[6]);
+  r.V = vel / r.L0vmax;
+  return r;
+}
+
+// mju_muscleGain engine_util_misc.c:529-571: muscle active force
+MJH_HD double muscleGain(double len, double vel, const double lengthrange[2], double acc0,
+                         const double* prm) {
+  const MuscleNorm n = muscleNorm(len, vel, lengthrange, acc0, prm);
+  const double fvmax = prm[8];
+  const double FL = muscleGainLength(n.L, prm[4], prm[5]);
+  double FV;
+  const double y = fvmax-1, V = n.V;
+  if (V <= -1) {
+    FV = 0;
+  } else if (V <= 0) {
+    FV = (V+1)*(V+1);
+  } else if (V <= y) {
+    FV = fvmax - (y-V)*(y-V) / max2(MINVAL, y);
+  } else {
+    FV = fvmax;
+  }
+  return -n.force*FL*FV;
+}
+
+// mjd_muscleGain_vel engine_derivative.c:762-807: derivative of muscleGain in velocity
+MJH_HD double muscleGainVel(double len, double vel, const double lengthrange[2], double acc0,
+                            const double* prm) {
+  const MuscleNorm n = muscleNorm(len, vel, lengthrange, acc0, prm);
+  const double FL = muscleGainLength(n.L, prm[4], prm[5]);
+  double dFV;
+  const double y = prm[8]-1, V = n.V;
+  if (V <= -1) {
+    dFV = 0;
+  } else if (V <= 0) {
+    dFV = 2*V + 2;
+  } else if (V <= y) {
+    dFV = (-2*V + 2*y) / max2(MINVAL, y);
+  } else {
+    dFV = 0;
+  }
+  return -n.force*FL*dFV/n.L0vmax;
+}
+
+// mju_muscleBias engine_util_misc.c:575-607: muscle passive force
+MJH_HD double muscleBias(double len, const double lengthrange[2], double acc0,
+                         const double* prm) {
+  const MuscleNorm n = muscleNorm(len, 0, lengthrange, acc0, prm);
+  const double fpmax = prm[7], L = n.L;
+  const double b = 0.5*(1+prm[5]);         // half-quadratic to (L0+lmax)/2, linear beyond
+  if (L <= 1) {
+    return 0;
+  } else if (L <= b) {
+    const double x = (L-1) / max2(MINVAL, b-1);
+    return -n.force*fpmax*0.5*x*x;
+  } else {
+    const double x = (L-b) / max2(MINVAL, b-1);
+    return -n.force*fpmax*(0.5 + x);
+  }
+}
+
+// mju_muscleDynamicsTimescale engine_util_misc.c:611-627
+MJH_HD double muscleDynamicsTimescale(double dctrl, double tau_act, double tau_deact,
+                                      double smoothing_width) {
+  if (smoothing_width < MINVAL) return dctrl > 0 ? tau_act : tau_deact;   // hard switching
+  return tau_deact + (tau_act-tau_deact)*sigmoid(dctrl/smoothing_width + 0.5);
+}
+
+// mju_muscleDynamics engine_util_misc.c:631-649, prm = (tau_act, tau_deact, smoothing_width)
+MJH_HD double muscleDynamics(double ctrl, double act, const double* prm) {
+  const double ctrlclamp = clip(ctrl, 0, 1);
+  const double actclamp = clip(act, 0, 1);
+  const double tau_act = prm[0] * (0.5 + 1.5*actclamp);       // Millard et al. (2013)
+  const double tau_deact = prm[1] / (0.5 + 1.5*actclamp);
+  const double dctrl = ctrlclamp - act;
+  const double tau = muscleDynamicsTimescale(dctrl, tau_act, tau_deact, prm[2]);
+  return dctrl / max2(MINVAL, tau);
+}
+
+// nextActivation engine_forward.c:236-259: act after one step of act_dot, clamped to actrange
+MJH_HD double nextActivation(const mjhipModel& m, int i, double act, double act_dot) {
+  if (m.actuator_dyntype[i] == mjhipDYN_FILTEREXACT) {
+    // act(h) = act(0) + act_dot(0) * tau * (1 - exp(-h / tau))
+    const double tau = max2(MINVAL, m.actuator_dynprm[10*i]);
+    act = act + act_dot * tau * (1 - exp(-m.opt.timestep / tau));
+  } else {
+    act = act + act_dot * m.opt.timestep;
+  }
+  if (m.actuator_actlimited[i]) {
+    act = clip(act, m.actuator_actrange[2*i], m.actuator_actrange[2*i+1]);
+  }
+  return act;
+}
+
 // dense value of the sparse actuator_moment row `i` at column `col`
 template <int S>
 MJH_HD double momentAt(const mjhipModel& m, const Lane<S>& d, int i, int col) {
@@ -7761,8 +7907,17 @@ MJH_HD double qDerivAt(const mjhipModel& m, const Lane<S>& d, int r, int c) {
     for (int i = 0; i < m.nu; i++) {
       double bias_vel = 0, gain_vel = 0;
       if (m.actuator_biastype[i] == mjhipBIAS_AFFINE) bias_vel = m.actuator_biasprm[10*i+2];
-      if (m.actuator_gaintype[i] == mjhipGAIN_AFFINE) gain_vel = m.actuator_gainprm[10*i+2];
-      if (gain_vel != 0) bias_vel += gain_vel * d.ctrl[i];
+      if (m.actuator_gaintype[i] == mjhipGAIN_AFFINE) {
+        gain_vel = m.actuator_gainprm[10*i+2];
+      } else if (m.actuator_gaintype[i] == mjhipGAIN_MUSCLE) {
+        gain_vel = muscleGainVel(d.actuator_length[i], d.actuator_velocity[i],
+                                 m.actuator_lengthrange + 2*i, m.actuator_acc0[i],
+                                 m.actuator_gainprm + 10*i);
+      }
+      if (gain_vel != 0) {                 // force = gain .* [ctrl | act] (:855-863)
+        bias_vel += gain_vel * (m.actuator_dyntype[i] == mjhipDYN_NONE ? d.ctrl[i]
+                                : d.act[m.actuator_actadr[i] + m.actuator_actnum[i] - 1]);
+      }
       if (bias_vel != 0) {
         double mr = momentAt(m, d, i, r);
         if (mr) q += momentAt(m, d, i, c) * (mr * bias_vel);
@@ -9430,8 +9585,14 @@ MJH_HD int constraintOnly(const mjhipModel& m, const Lane<S>& d) {
 
 //---------------------------------- engine_forward.c (constraint-free) ----------------------
 
-// mj_fwdActuation :276-515 for joint transmissions with fixed/affine gain and none/affine
-// bias (the actuator subset accepted at context creation); ctrl clamped by ctrlrange
+// mj_fwdActuation :276-515: the ctrl clamp, act_dot of the stateful actuators (integrator,
+// filter / filterexact, muscle), force = gain * [ctrl | act] + bias with fixed / affine /
+// muscle gain and none / affine / muscle bias (actearly: the force sees nextActivation), the
+// force clamp, qfrc_actuator = moment' force. It also stores act_next, the activation
+// mj_advance's loop (:738-750) would write over act. User dynamics, gain and bias are
+// rejected at the entry points; no actuator is disabled (mj_actuatorDisabled's groups are
+// not carried). A stateless fixed / affine actuator takes exactly the operations it took
+// before activations were an input.
 template <int S>
 MJH_HD void fwdActuation(const mjhipModel& m, const Lane<S>& d) {
   const int nv = m.nv, nu = m.nu;
@@ -9444,15 +9605,49 @@ MJH_HD void fwdActuation(const mjhipModel& m, const Lane<S>& d) {
       const double* r = m.actuator_ctrlrange + 2*i;
       ctrl = ctrl < r[0] ? r[0] : (ctrl > r[1] ? r[1] : ctrl);
     }
+    // the actuator's last activation variable (actnum is 1 for every dyntype carried)
+    const int adr = m.actuator_actadr[i] < 0 ? -1 : m.actuator_actadr[i] + m.actuator_actnum[i] - 1;
+    double act = 0, act_dot = 0;
+    if (adr >= 0) {
+      act = d.act[adr];
+      const double* dp = m.actuator_dynprm + 10*i;
+      switch (m.actuator_dyntype[i]) {
+        case mjhipDYN_INTEGRATOR:
+          act_dot = ctrl;
+          break;
+        case mjhipDYN_FILTER:
+        case mjhipDYN_FILTEREXACT:
+          act_dot = (ctrl - act) / max2(MINVAL, dp[0]);
+          break;
+        case mjhipDYN_MUSCLE:
+          act_dot = muscleDynamics(ctrl, act, dp);
+          break;
+        default:                           // user dynamics without a callback: act_dot = 0
+          break;
+      }
+      d.act_dot[adr] = act_dot;
+      d.act_next[adr] = nextActivation(m, i, act, act_dot);
+    }
     const double* prm = m.actuator_gainprm + 10*i;
     double gain = prm[0];
     if (m.actuator_gaintype[i] == mjhipGAIN_AFFINE) {
       gain = prm[0] + prm[1]*d.actuator_length[i] + prm[2]*d.actuator_velocity[i];
+    } else if (m.actuator_gaintype[i] == mjhipGAIN_MUSCLE) {
+      gain = muscleGain(d.actuator_length[i], d.actuator_velocity[i],
+                        m.actuator_lengthrange + 2*i, m.actuator_acc0[i], prm);
     }
-    double f = gain * ctrl;
+    double f;
+    if (adr < 0) {
+      f = gain * ctrl;
+    } else {
+      f = gain * (m.actuator_actearly[i] ? nextActivation(m, i, act, act_dot) : act);
+    }
     if (m.actuator_biastype[i] == mjhipBIAS_AFFINE) {
       prm = m.actuator_biasprm + 10*i;
       f += prm[0] + prm[1]*d.actuator_length[i] + prm[2]*d.actuator_velocity[i];
+    } else if (m.actuator_biastype[i] == mjhipBIAS_MUSCLE) {
+      f += muscleBias(d.actuator_length[i], m.actuator_lengthrange + 2*i, m.actuator_acc0[i],
+                      m.actuator_biasprm + 10*i);
     }
     if (m.actuator_forcelimited[i]) {
       const double* r = m.actuator_forcerange + 2*i;
@@ -9511,28 +9706,47 @@ MJH_HD int forwardSkip(const mjhipModel& m, const Lane<S>& d, int skipstage) {
 
 //---------------------------------- device mirror (include/mjhip.h layout) ------------------
 
+// Passed by value to every kernel beside mjhipModel: HIP's kernel-argument limit is 4,096 B
+// and hipcc does not diagnose a breach, so all pointers come first and then all counts (a
+// pointer next to its int count costs 4 B of padding per field); mjhip.hip asserts the sum.
 struct Mirror {
-#define XD(name, d0, d1, stage) double* name; int name##_n;
+#define XD(name, d0, d1, stage) double* name;
   MJHIP_DATA_FIELDS
   MJHIP_DATA_FORWARD
 #undef XD
-#define XSC(name, n) double* name; int name##_n;
+#define XSC(name, n) double* name;
   MJHIP_SCRATCH_FIELDS
 #undef XSC
-#define XSI(name, n) int* name; int name##_n;
+#define XSI(name, n) int* name;
+  MJHIP_SCRATCH_INT_FIELDS
+#undef XSI
+  const CoopPair* prog;                      // the static collision program (Lane::prog)
+  const int* prog_ipair;
+#define XD(name, d0, d1, stage) double* name;
+  MJHIP_DATA_ACTIVATION
+#undef XD
+  long nj_cap;
+#define XD(name, d0, d1, stage) int name##_n;
+  MJHIP_DATA_FIELDS
+  MJHIP_DATA_FORWARD
+#undef XD
+#define XSC(name, n) int name##_n;
+  MJHIP_SCRATCH_FIELDS
+#undef XSC
+#define XSI(name, n) int name##_n;
   MJHIP_SCRATCH_INT_FIELDS
 #undef XSI
   int efc_cap;
   int con_cap;
-  long nj_cap;
-  const CoopPair* prog;                      // the static collision program (Lane::prog)
-  const int* prog_ipair;
   int nprog;
   // mjd_inverseFD's perturbed instances (codegen.FD_KEEP): fd_elide set, the generated
   // kernels' FD instantiation drops, from instance block full_blk on, the stores no later
   // kernel reads
   int fd_elide;
   int full_blk;
+#define XD(name, d0, d1, stage) int name##_n;
+  MJHIP_DATA_ACTIVATION
+#undef XD
 };
 
 MJH_HD mjh::Lane<64> lane_view(const Mirror& mr, int blk, int lane) {
@@ -9572,6 +9786,9 @@ MJH_HD mjh::Lane<64> lane_view(const Mirror& mr, int blk, int lane) {
   d.dchain = nullptr;
   d.ccdx = mr.ccd + ((long)blk*mr.ccd_n)*64 + (long)lane*mr.ccd_n;
   d.ccdxi = mr.ccdi + ((long)blk*mr.ccdi_n)*64 + (long)lane*mr.ccdi_n;
+#define XD(name, d0, d1, stage) d.name.p = mr.name + ((long)blk*mr.name##_n)*64 + lane;
+  MJHIP_DATA_ACTIVATION
+#undef XD
   return d;
 }
 

@@ -33,6 +33,12 @@ extern template __global__ void k_constraint_coop<8, true, false, false>(mjhipMo
 extern template __global__ void k_constraint_coop<32, true, false, false>(mjhipModel, Mirror, int, const int*, const int*, const CoopPair*, const mjh::ContactParam*, const unsigned long long*, int, double*, int*, int*);
 #include "post_pass.h"
 
+// Every kernel takes mjhipModel and Mirror by value, and HIP's kernel-argument segment holds
+// 4,096 B (a larger one compiles without a diagnostic and fails at launch). 160 B is the room
+// the widest argument list beside the two (k_fd_expand, k_fd_diff, k_constraint_coop) takes.
+static_assert(sizeof(mjhipModel) + sizeof(Mirror) + 160 <= 4096,
+              "mjhipModel + Mirror leave no room in the 4,096 B kernel-argument segment");
+
 //==================================== kernels ===============================================
 
 // k_constraint, k_constraint_coop (kern_constraint.hip) and k_inverse (kern_inverse.hip):
@@ -168,7 +174,7 @@ __device__ static inline long fd_inst(int layout, long nbase, long b, int p, int
 
 // instances [first, end) of the layout (first a multiple of 64), one block per 64 instances,
 // its kExpandWaves waves taking turns over the input components: qvel[k], qacc[k] (k < nv), joint j's
-// qpos (mj_integratePos on dof i for the qpos perturbations), ctrl[k]. The 64 lanes of a wave
+// qpos (mj_integratePos on dof i for the qpos perturbations), ctrl[k], act[k]. The 64 lanes of a wave
 // write one 512-byte mirror line per value. gate: the stage-skip fall-back's expansion (mjhip_inverseFDBatch): it runs only when
 // k_vaskip found a centre with limit rows (fdflag[0]), and its first thread hands the range
 // {first, end} -- or the empty {first, first} -- to the fall-back k_all (fdflag[1..2])
@@ -203,11 +209,13 @@ __global__ __launch_bounds__(64*kExpandWaves) void k_fd_expand(mjhipModel m, Mir
                                                   const double* __restrict__ qpos,
                                                   const double* __restrict__ qvel,
                                                   const double* __restrict__ qacc,
-                                                  const double* __restrict__ ctrl, double eps,
+                                                  const double* __restrict__ ctrl,
+                                                  const double* __restrict__ act, double eps,
                                                   int layout, int* __restrict__ fdflag,
                                                   long first, long end, int gate) {
   const int nv = m.nv, nq = m.nq, P = 3*nv + 1;
-  const int ncomp = 2*nv + m.njnt + (ctrl ? m.nu : 0);
+  const int nctrl = ctrl ? m.nu : 0;
+  const int ncomp = 2*nv + m.njnt + nctrl + (act ? m.na : 0);
   // blocks of blockDim.x / 64 waves, striding over the 64-instance blocks of [first, end)
   // (the main expansion: one block each; the gated one: a few one-wave blocks, so that the
   // usual empty launch dispatches little): wave w writes components w, w + waves, ...
@@ -239,6 +247,11 @@ __global__ __launch_bounds__(64*kExpandWaves) void k_fd_expand(mjhipModel m, Mir
     const int k = comp - nv;
     const double x = qacc[b*nv + k];
     d.qacc[k] = p - 1 == k ? x + eps : x;
+    continue;
+  }
+  if (comp >= 2*nv + m.njnt + nctrl) {   // flg_actuation: the base state's activations
+    const int k = comp - 2*nv - m.njnt - nctrl;
+    d.act[k] = act[b*m.na + k];
     continue;
   }
   if (comp >= 2*nv + m.njnt) {           // flg_actuation: the base state's controls
@@ -397,15 +410,54 @@ __global__ __launch_bounds__(64) void k_assemble(mjhipModel m, Mirror mr, int B,
   if (k == 0 && status && cstat[inst]) status[inst] |= cstat[inst];
 }
 
+// Batched mj_fwdActuation (mjh::fwdActuation) over the actuator_length, actuator_velocity and
+// actuator_moment already in the mirror: one lane per instance, 64-instance blocks, so a
+// wave's read or write of one component of a mirror field is one 512-byte segment. Optional
+// row-major ctrl / act are copied into the mirror first; optional row-major act_dot, act_next
+// and qfrc_actuator are written at the end. mj_fwdActuation raises no per-instance condition
+// on this path, so every status word is 0.
+__global__ __launch_bounds__(64) void k_actuation(mjhipModel m, Mirror mr, int B,
+                                                  const double* __restrict__ ctrl_in,
+                                                  const double* __restrict__ act_in,
+                                                  double* __restrict__ act_dot_out,
+                                                  double* __restrict__ act_next_out,
+                                                  double* __restrict__ qfrc_out,
+                                                  int* __restrict__ status) {
+  const int blk = blockIdx.x, lane = threadIdx.x;
+  const long inst = (long)blk*64 + lane;
+  if (inst >= B) return;
+  Lane<64> d = lane_view(mr, blk, lane);
+  if (ctrl_in) {
+    for (int k = 0; k < m.nu; k++) d.ctrl[k] = ctrl_in[inst*m.nu + k];
+  }
+  if (act_in) {
+    for (int k = 0; k < m.na; k++) d.act[k] = act_in[inst*m.na + k];
+  }
+  mjh::fwdActuation(m, d);
+  if (act_dot_out) {
+    for (int k = 0; k < m.na; k++) act_dot_out[inst*m.na + k] = d.act_dot[k];
+  }
+  if (act_next_out) {
+    for (int k = 0; k < m.na; k++) act_next_out[inst*m.na + k] = d.act_next[k];
+  }
+  if (qfrc_out) {
+    for (int k = 0; k < m.nv; k++) qfrc_out[inst*m.nv + k] = d.qfrc_actuator[k];
+  }
+  if (status) status[inst] = 0;
+}
+
 // Constraint-free mj_forward over a batch (mjh::forwardSkip). Optional row-major qpos, qvel,
-// ctrl are copied into the mirror first; qfrc_applied / xfrc_applied are read from the
+// ctrl, act are copied into the mirror first; qfrc_applied / xfrc_applied are read from the
 // mirror; optional row-major qacc is written at the end.
 template <bool CONTACT>
 __global__ __launch_bounds__(64) void k_forward(mjhipModel m, Mirror mr, int B,
                                                 const double* __restrict__ qpos_in,
                                                 const double* __restrict__ qvel_in,
                                                 const double* __restrict__ ctrl_in,
+                                                const double* __restrict__ act_in,
                                                 double* __restrict__ qacc_out,
+                                                double* __restrict__ act_dot_out,
+                                                double* __restrict__ act_next_out,
                                                 int* __restrict__ status) {
   const int blk = blockIdx.x, lane = threadIdx.x;
   const long inst = (long)blk*64 + lane;
@@ -420,9 +472,18 @@ __global__ __launch_bounds__(64) void k_forward(mjhipModel m, Mirror mr, int B,
   if (ctrl_in) {
     for (int k = 0; k < m.nu; k++) d.ctrl[k] = ctrl_in[inst*m.nu + k];
   }
+  if (act_in) {
+    for (int k = 0; k < m.na; k++) d.act[k] = act_in[inst*m.na + k];
+  }
   int st = mjh::forwardSkip<64, CONTACT>(m, d, mjhipSTAGE_NONE);
   if (qacc_out) {
     for (int k = 0; k < m.nv; k++) qacc_out[inst*m.nv + k] = d.qacc[k];
+  }
+  if (act_dot_out) {
+    for (int k = 0; k < m.na; k++) act_dot_out[inst*m.na + k] = d.act_dot[k];
+  }
+  if (act_next_out) {
+    for (int k = 0; k < m.na; k++) act_next_out[inst*m.na + k] = d.act_next[k];
   }
   if (status) status[inst] = st;
 }
@@ -522,8 +583,38 @@ struct mjhipContext_ {
   hipEvent_t tev0 = nullptr, tev1 = nullptr;
 };
 
+// 1 when the model has activation states or a muscle gain / bias: only then are the arrays
+// of MJHIP_MODEL_POINTERS_A read. They sit behind every older pointer of mjhipModel, so a
+// caller compiled against a header without them passes a shorter struct, and for the models
+// such a caller can describe the library never looks past its end.
+static bool mjhip_modelUsesActivation(const mjhipModel* m) {
+  if (m->na > 0) return true;
+  for (int i = 0; i < m->nu; i++) {
+    if (m->actuator_gaintype[i] == mjhipGAIN_MUSCLE || m->actuator_biastype[i] == mjhipBIAS_MUSCLE) {
+      return true;
+    }
+  }
+  return false;
+}
+
+// the model as the library reads it: *m, or its older prefix with the activation arrays absent
+static mjhipModel model_read(const mjhipModel* m) {
+  mjhipModel r;
+  if (mjhip_modelUsesActivation(m)) {
+    r = *m;
+  } else {
+    memcpy(&r, m, offsetof(mjhipModel, actuator_actadr));
+#define X(type, name, d0, d1) r.name = nullptr;
+    MJHIP_MODEL_POINTERS_A
+#undef X
+  }
+  return r;
+}
+
 // FNV-1a 64 over sizes, options and every model array (= fields.model_signature in Python)
-static unsigned long long model_signature(const mjhipModel* m) {
+static unsigned long long model_signature(const mjhipModel* caller) {
+  const mjhipModel rd = model_read(caller);
+  const mjhipModel* m = &rd;
   unsigned long long h = 0xcbf29ce484222325ull;
   auto feed = [&](const void* p, size_t n) {
     const unsigned char* b = (const unsigned char*)p;
@@ -658,6 +749,7 @@ MJHIP_API int mjhip_fieldSize(const mjhipModel* m, const char* name) {
 #define XD(nm, d0, d1, stage) if (!strcmp(name, #nm)) return (m->d0) * (d1);
   MJHIP_DATA_FIELDS
   MJHIP_DATA_FORWARD
+  MJHIP_DATA_ACTIVATION
 #undef XD
 #undef MJ_M
   return -1;
@@ -678,12 +770,14 @@ MJHIP_API int mjhip_contextCreate(const mjhipModel* m, int device, int capacity,
   return mjhip_contextCreateCapped(m, device, capacity, 0, 0, out);
 }
 
-MJHIP_API int mjhip_contextCreateCapped(const mjhipModel* m, int device, int capacity,
+MJHIP_API int mjhip_contextCreateCapped(const mjhipModel* caller, int device, int capacity,
                                         int max_contacts, int max_rows, mjhipContext** out) {
-  if (!m || !out || capacity <= 0 || max_contacts < 0 || max_rows < 0) {
+  if (!caller || !out || capacity <= 0 || max_contacts < 0 || max_rows < 0) {
     set_error("mjhip_contextCreate: bad argument");
     return MJHIP_ERR_ARG;
   }
+  const mjhipModel rd = model_read(caller);
+  const mjhipModel* m = &rd;
   *out = nullptr;
   int ndev = mjhip_deviceCount();
   if (ndev <= 0) {
@@ -734,6 +828,18 @@ MJHIP_API int mjhip_contextCreateCapped(const mjhipModel* m, int device, int cap
   MJHIP_MODEL_POINTERS
 #undef X
 #undef MJ_M
+  if (m->nu && (!m->actuator_actadr || !m->actuator_actnum)) {
+    // a caller that does not fill the activation addresses gets the compiler's: consecutive
+    // addresses, one activation per stateful actuator, -1 / 0 for dyntype none (the zeros an
+    // absent array uploads as would alias every actuator to act[0])
+    int* adr = (int*)(hbuf.data() + ((char*)c->dmodel.actuator_actadr - (char*)c->dmodel_buf));
+    int* num = (int*)(hbuf.data() + ((char*)c->dmodel.actuator_actnum - (char*)c->dmodel_buf));
+    for (int i = 0, k = 0; i < m->nu; i++) {
+      const bool st = m->actuator_dyntype[i] != mjhipDYN_NONE;
+      adr[i] = st ? k++ : -1;
+      num[i] = st ? 1 : 0;
+    }
+  }
   if (hipMemcpy(c->dmodel_buf, hbuf.data(), hbuf.size(), hipMemcpyHostToDevice) != hipSuccess) {
     set_error("model upload failed");
     hipFree(c->dmodel_buf);
@@ -760,6 +866,10 @@ MJHIP_API int mjhip_contextCreateCapped(const mjhipModel* m, int device, int cap
   mb += align256(sizeof(int) * nblk * 64 * (size_t)c->mirror.name##_n); }
   MJHIP_SCRATCH_INT_FIELDS
 #undef XSI
+#define XD(name, d0, d1, stage) c->mirror.name##_n = (m->d0) * (d1); \
+  mb += align256(sizeof(double) * nblk * 64 * (size_t)c->mirror.name##_n);
+  MJHIP_DATA_ACTIVATION
+#undef XD
   (void)nv; (void)efc_cap; (void)con_cap;
   c->mirror.efc_cap = c->efc_cap;
   c->mirror.con_cap = c->con_cap;
@@ -802,6 +912,13 @@ MJHIP_API int mjhip_contextCreateCapped(const mjhipModel* m, int device, int cap
 #undef XSIC
 #define XSCC(name, n) XSC(name, n)
 #define XSIC(name, n) XSI(name, n)
+  // the activation state, after every other field; act is zero from the fill above, as
+  // mj_resetData leaves it
+#define XD(name, d0, d1, stage) c->mirror.name = (double*)p; \
+  c->fields[#name] = {c->mirror.name, c->mirror.name##_n}; \
+  p += align256(sizeof(double) * nblk * 64 * (size_t)c->mirror.name##_n);
+  MJHIP_DATA_ACTIVATION
+#undef XD
 #undef MJ_M
   // every failure below releases the partial context through mjhip_contextFree
   auto fail = [&](const char* what) {
@@ -809,8 +926,10 @@ MJHIP_API int mjhip_contextCreateCapped(const mjhipModel* m, int device, int cap
     mjhip_contextFree(c);
     return MJHIP_ERR_HIP;
   };
-  // staging: row-major qpos, qvel, qacc, qfrc for `capacity` instances
-  c->stage_bytes = sizeof(double) * (size_t)c->capacity * (m->nq + 3*(size_t)m->nv + m->nu);
+  // staging: row-major qpos, qvel, qacc, qfrc, ctrl, then act, act_dot, act_next for
+  // `capacity` instances
+  c->stage_bytes = sizeof(double) * (size_t)c->capacity *
+                   (m->nq + 3*(size_t)m->nv + m->nu + 3*(size_t)m->na);
   if (hipMalloc((void**)&c->stage, c->stage_bytes) != hipSuccess ||
       hipMalloc((void**)&c->status, sizeof(int) * (size_t)c->capacity) != hipSuccess) {
     return fail("hipMalloc(staging)");
@@ -1662,8 +1781,66 @@ MJHIP_API int mjhip_inverseBatch(mjhipContext* c, int B, const mjtNum* qpos,
   return anybad ? MJHIP_ERR_INSTANCE : MJHIP_OK;
 }
 
-MJHIP_API int mjhip_forwardBatch(mjhipContext* c, int B, const mjtNum* qpos, const mjtNum* qvel,
-                                 const mjtNum* ctrl, mjtNum* qacc, int flags, int* status) {
+// the actuator subset of the entry points that take no activations (mjhip_forwardBatch,
+// mjhip_inverseFDBatchEx): fixed/affine gain, none/affine bias, no activation dynamics
+static const char* actuation_stateless(const mjhipModel& m) {
+  for (int i = 0; i < m.nu; i++) {
+    if ((m.actuator_gaintype[i] != mjhipGAIN_FIXED && m.actuator_gaintype[i] != mjhipGAIN_AFFINE) ||
+        (m.actuator_biastype[i] != mjhipBIAS_NONE && m.actuator_biastype[i] != mjhipBIAS_AFFINE) ||
+        m.actuator_dyntype[i] != mjhipDYN_NONE) {
+      return "muscle/user gain or bias, or actuator dynamics (act)";
+    }
+  }
+  return nullptr;
+}
+
+// the actuator subset of the device mj_fwdActuation (mjh::fwdActuation): every dynamics, gain
+// and bias type but the user callbacks, one activation per stateful actuator
+static const char* actuation_unsupported(const mjhipModel& m) {
+  for (int i = 0; i < m.nu; i++) {
+    if (m.actuator_dyntype[i] < mjhipDYN_NONE || m.actuator_dyntype[i] >= mjhipDYN_USER ||
+        m.actuator_gaintype[i] < mjhipGAIN_FIXED || m.actuator_gaintype[i] >= mjhipGAIN_USER ||
+        m.actuator_biastype[i] < mjhipBIAS_NONE || m.actuator_biastype[i] >= mjhipBIAS_USER) {
+      return "user actuator dynamics, gain or bias";
+    }
+    if (m.actuator_actnum && m.actuator_actnum[i] > 1) return "an actuator with actdim > 1";
+  }
+  return nullptr;
+}
+
+// the staging slices behind qpos, qvel, qacc, qfrc (stage layout of mjhip_contextCreate)
+struct StageAct {
+  double *ctrl, *act, *act_dot, *act_next;
+};
+static StageAct stage_act(mjhipContext* c) {
+  const mjhipModel& m = c->hmodel;
+  StageAct s;
+  s.ctrl = c->stage + (size_t)c->capacity*(m.nq + 3*(size_t)m.nv);
+  s.act = s.ctrl + (size_t)c->capacity*m.nu;
+  s.act_dot = s.act + (size_t)c->capacity*m.na;
+  s.act_next = s.act_dot + (size_t)c->capacity*m.na;
+  return s;
+}
+
+// the per-instance status words of the call that just ran, as every batch entry point
+// returns them
+static int collect_status(mjhipContext* c, int B, int* status, bool want) {
+  int anybad = 0;
+  if (want) {
+    std::vector<int> st(B);
+    HIPCHECK(hipMemcpyAsync(st.data(), c->status, sizeof(int)*(size_t)B, hipMemcpyDeviceToHost,
+                            c->stream));
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    for (int i = 0; i < B; i++) anybad |= st[i];
+    if (status) memcpy(status, st.data(), sizeof(int)*(size_t)B);
+  }
+  return anybad ? MJHIP_ERR_INSTANCE : MJHIP_OK;
+}
+
+MJHIP_API int mjhip_forwardBatchEx(mjhipContext* c, int B, const mjtNum* qpos,
+                                   const mjtNum* qvel, const mjtNum* ctrl, const mjtNum* act,
+                                   mjtNum* qacc, mjtNum* act_dot, mjtNum* act_next, int flags,
+                                   int* status) {
   if (!c || B < 0) {
     set_error("mjhip_forwardBatch: bad argument");
     return MJHIP_ERR_ARG;
@@ -1673,67 +1850,140 @@ MJHIP_API int mjhip_forwardBatch(mjhipContext* c, int B, const mjtNum* qpos, con
     return MJHIP_ERR_CAPACITY;
   }
   const mjhipModel& m = c->hmodel;
-  for (int i = 0; i < m.nu; i++) {
-    if ((m.actuator_gaintype[i] != mjhipGAIN_FIXED && m.actuator_gaintype[i] != mjhipGAIN_AFFINE) ||
-        (m.actuator_biastype[i] != mjhipBIAS_NONE && m.actuator_biastype[i] != mjhipBIAS_AFFINE) ||
-        m.actuator_dyntype[i] != mjhipDYN_NONE) {
-      set_error("mjhip_forwardBatch: muscle/user gain or bias, or actuator dynamics (act), "
-                "is not supported");
-      return MJHIP_ERR_MODEL;
-    }
+  if (const char* why = actuation_unsupported(m)) {
+    set_error("mjhip_forwardBatch: %s is not supported", why);
+    return MJHIP_ERR_MODEL;
   }
   if (B == 0) return MJHIP_OK;
   HIPCHECK(hipSetDevice(c->device));
   const bool dev = flags & MJHIP_FLAG_DEVICE_PTRS;
   const bool mirror_in = flags & MJHIP_FLAG_MIRROR_INPUT;
-  const double *dq = nullptr, *dv = nullptr, *dc = nullptr;
+  const double *dq = nullptr, *dv = nullptr, *dc = nullptr, *dact = nullptr;
   double* sq = c->stage;
   double* sv = sq + (size_t)c->capacity*m.nq;
   double* sa = sv + (size_t)c->capacity*m.nv;
-  double* sc = sa + 2*(size_t)c->capacity*m.nv;
+  const StageAct sx = stage_act(c);
   if (!mirror_in) {
     if (!qpos || !qvel) {
       set_error("mjhip_forwardBatch: qpos/qvel required without MJHIP_FLAG_MIRROR_INPUT");
       return MJHIP_ERR_ARG;
     }
     if (dev) {
-      dq = qpos; dv = qvel; dc = ctrl;
+      dq = qpos; dv = qvel; dc = ctrl; dact = m.na ? act : nullptr;
     } else {
       HIPCHECK(hipMemcpyAsync(sq, qpos, sizeof(double)*(size_t)B*m.nq, hipMemcpyHostToDevice,
                               c->stream));
       HIPCHECK(hipMemcpyAsync(sv, qvel, sizeof(double)*(size_t)B*m.nv, hipMemcpyHostToDevice,
                               c->stream));
       if (ctrl && m.nu) {
-        HIPCHECK(hipMemcpyAsync(sc, ctrl, sizeof(double)*(size_t)B*m.nu, hipMemcpyHostToDevice,
-                                c->stream));
+        HIPCHECK(hipMemcpyAsync(sx.ctrl, ctrl, sizeof(double)*(size_t)B*m.nu,
+                                hipMemcpyHostToDevice, c->stream));
       }
-      dq = sq; dv = sv; dc = (ctrl && m.nu) ? sc : nullptr;
+      if (act && m.na) {
+        HIPCHECK(hipMemcpyAsync(sx.act, act, sizeof(double)*(size_t)B*m.na,
+                                hipMemcpyHostToDevice, c->stream));
+      }
+      dq = sq; dv = sv; dc = (ctrl && m.nu) ? sx.ctrl : nullptr;
+      dact = (act && m.na) ? sx.act : nullptr;
     }
   }
   double* dqacc = qacc ? (dev ? qacc : sa) : nullptr;
+  double* ddot = (act_dot && m.na) ? (dev ? act_dot : sx.act_dot) : nullptr;
+  double* dnext = (act_next && m.na) ? (dev ? act_next : sx.act_next) : nullptr;
   dim3 grid((B + 63) / 64), block(64);
   if (c->con_cap > 0) {
     hipLaunchKernelGGL(k_forward<true>, grid, block, 0, c->stream, c->dmodel, c->mirror, B, dq,
-                       dv, dc, dqacc, c->status);
+                       dv, dc, dact, dqacc, ddot, dnext, c->status);
   } else {
     hipLaunchKernelGGL(k_forward<false>, grid, block, 0, c->stream, c->dmodel, c->mirror, B, dq,
-                       dv, dc, dqacc, c->status);
+                       dv, dc, dact, dqacc, ddot, dnext, c->status);
   }
   HIPCHECK(hipGetLastError());
-  if (qacc && !dev) {
-    HIPCHECK(hipMemcpyAsync(qacc, sa, sizeof(double)*(size_t)B*m.nv, hipMemcpyDeviceToHost,
-                            c->stream));
+  if (!dev) {
+    if (qacc) {
+      HIPCHECK(hipMemcpyAsync(qacc, sa, sizeof(double)*(size_t)B*m.nv, hipMemcpyDeviceToHost,
+                              c->stream));
+    }
+    if (ddot) {
+      HIPCHECK(hipMemcpyAsync(act_dot, ddot, sizeof(double)*(size_t)B*m.na,
+                              hipMemcpyDeviceToHost, c->stream));
+    }
+    if (dnext) {
+      HIPCHECK(hipMemcpyAsync(act_next, dnext, sizeof(double)*(size_t)B*m.na,
+                              hipMemcpyDeviceToHost, c->stream));
+    }
   }
-  int anybad = 0;
-  if (status || !dev) {
-    std::vector<int> st(B);
-    HIPCHECK(hipMemcpyAsync(st.data(), c->status, sizeof(int)*(size_t)B, hipMemcpyDeviceToHost,
-                            c->stream));
-    HIPCHECK(hipStreamSynchronize(c->stream));
-    for (int i = 0; i < B; i++) anybad |= st[i];
-    if (status) memcpy(status, st.data(), sizeof(int)*(size_t)B);
+  return collect_status(c, B, status, status || !dev);
+}
+
+MJHIP_API int mjhip_forwardBatch(mjhipContext* c, int B, const mjtNum* qpos, const mjtNum* qvel,
+                                 const mjtNum* ctrl, mjtNum* qacc, int flags, int* status) {
+  if (c) {
+    if (const char* why = actuation_stateless(c->hmodel)) {
+      set_error("mjhip_forwardBatch: %s is not supported (mjhip_forwardBatchEx takes act)", why);
+      return MJHIP_ERR_MODEL;
+    }
   }
-  return anybad ? MJHIP_ERR_INSTANCE : MJHIP_OK;
+  return mjhip_forwardBatchEx(c, B, qpos, qvel, ctrl, nullptr, qacc, nullptr, nullptr, flags,
+                              status);
+}
+
+MJHIP_API int mjhip_actuationBatch(mjhipContext* c, int B, const mjtNum* ctrl,
+                                   const mjtNum* act, mjtNum* act_dot, mjtNum* act_next,
+                                   mjtNum* qfrc_actuator, int flags, int* status) {
+  if (!c || B < 0) {
+    set_error("mjhip_actuationBatch: bad argument");
+    return MJHIP_ERR_ARG;
+  }
+  if (B > c->capacity) {
+    set_error("batch %d exceeds context capacity %d", B, c->capacity);
+    return MJHIP_ERR_CAPACITY;
+  }
+  const mjhipModel& m = c->hmodel;
+  if (const char* why = actuation_unsupported(m)) {
+    set_error("mjhip_actuationBatch: %s is not supported", why);
+    return MJHIP_ERR_MODEL;
+  }
+  if (B == 0) return MJHIP_OK;
+  HIPCHECK(hipSetDevice(c->device));
+  const bool dev = flags & MJHIP_FLAG_DEVICE_PTRS;
+  const StageAct sx = stage_act(c);
+  double* sf = c->stage + (size_t)c->capacity*(m.nq + 2*(size_t)m.nv);   // the qfrc slice
+  const double* dc = (ctrl && m.nu) ? ctrl : nullptr;
+  const double* dact = (act && m.na) ? act : nullptr;
+  if (!dev) {
+    if (dc) {
+      HIPCHECK(hipMemcpyAsync(sx.ctrl, ctrl, sizeof(double)*(size_t)B*m.nu,
+                              hipMemcpyHostToDevice, c->stream));
+      dc = sx.ctrl;
+    }
+    if (dact) {
+      HIPCHECK(hipMemcpyAsync(sx.act, act, sizeof(double)*(size_t)B*m.na, hipMemcpyHostToDevice,
+                              c->stream));
+      dact = sx.act;
+    }
+  }
+  double* ddot = (act_dot && m.na) ? (dev ? act_dot : sx.act_dot) : nullptr;
+  double* dnext = (act_next && m.na) ? (dev ? act_next : sx.act_next) : nullptr;
+  double* dqf = qfrc_actuator ? (dev ? qfrc_actuator : sf) : nullptr;
+  hipLaunchKernelGGL(k_actuation, dim3((B + 63) / 64), dim3(64), 0, c->stream, c->dmodel,
+                     c->mirror, B, dc, dact, ddot, dnext, dqf, c->status);
+  HIPCHECK(hipGetLastError());
+  if (!dev) {
+    if (ddot) {
+      HIPCHECK(hipMemcpyAsync(act_dot, ddot, sizeof(double)*(size_t)B*m.na,
+                              hipMemcpyDeviceToHost, c->stream));
+    }
+    if (dnext) {
+      HIPCHECK(hipMemcpyAsync(act_next, dnext, sizeof(double)*(size_t)B*m.na,
+                              hipMemcpyDeviceToHost, c->stream));
+    }
+    if (dqf) {
+      HIPCHECK(hipMemcpyAsync(qfrc_actuator, dqf, sizeof(double)*(size_t)B*m.nv,
+                              hipMemcpyDeviceToHost, c->stream));
+    }
+  }
+  return collect_status(c, B, status, status || !dev);
 }
 
 MJHIP_API int mjhip_statusDownload(mjhipContext* c, int first, int count, int* dst) {
@@ -1888,25 +2138,13 @@ MJHIP_API int mjhip_timeInverseKernel(mjhipContext* c, int B, int reps, int skip
   return MJHIP_OK;
 }
 
-// actuator subset of the device mj_fwdActuation (mjh::fwdActuation): fixed/affine gain,
-// none/affine bias, no activation dynamics
-static const char* actuation_unsupported(const mjhipModel& m) {
-  for (int i = 0; i < m.nu; i++) {
-    if ((m.actuator_gaintype[i] != mjhipGAIN_FIXED && m.actuator_gaintype[i] != mjhipGAIN_AFFINE) ||
-        (m.actuator_biastype[i] != mjhipBIAS_NONE && m.actuator_biastype[i] != mjhipBIAS_AFFINE) ||
-        m.actuator_dyntype[i] != mjhipDYN_NONE) {
-      return "muscle/user gain or bias, or actuator dynamics (act)";
-    }
-  }
-  return nullptr;
-}
-
-MJHIP_API int mjhip_inverseFDBatchEx(mjhipContext* c, int B, const mjtNum* qpos,
-                                     const mjtNum* qvel, const mjtNum* qacc, const mjtNum* ctrl,
-                                     mjtNum eps, int flg_actuation, mjtNum* DfDq, mjtNum* DfDv,
-                                     mjtNum* DfDa, mjtNum* DsDq, mjtNum* DsDv, mjtNum* DsDa,
-                                     mjtNum* DmDq, int flags) {
-  if (!c || B <= 0 || !qpos || !qvel || !qacc || (flg_actuation && c->hmodel.nu && !ctrl)) {
+MJHIP_API int mjhip_inverseFDBatchAct(mjhipContext* c, int B, const mjtNum* qpos,
+                                      const mjtNum* qvel, const mjtNum* qacc, const mjtNum* ctrl,
+                                      const mjtNum* act, mjtNum eps, int flg_actuation,
+                                      mjtNum* DfDq, mjtNum* DfDv, mjtNum* DfDa, mjtNum* DsDq,
+                                      mjtNum* DsDv, mjtNum* DsDa, mjtNum* DmDq, int flags) {
+  if (!c || B <= 0 || !qpos || !qvel || !qacc || (flg_actuation && c->hmodel.nu && !ctrl) ||
+      (flg_actuation && c->hmodel.na && !act)) {
     set_error("mjhip_inverseFDBatch: bad argument");
     return MJHIP_ERR_ARG;
   }
@@ -1934,6 +2172,9 @@ MJHIP_API int mjhip_inverseFDBatchEx(mjhipContext* c, int B, const mjtNum* qpos,
   HIPCHECK(hipSetDevice(c->device));
   const bool dev = flags & MJHIP_FLAG_DEVICE_PTRS;
   const double *dq = qpos, *dv = qvel, *da = qacc, *dc = flg_actuation ? ctrl : nullptr;
+  // given activations reach every evaluation, with or without flg_actuation: the implicit
+  // mj_discreteAcc of an mjENBL_INVDISCRETE model reads them too (mjd_actuator_vel)
+  const double* dact = m.na ? act : nullptr;
   // per-call device buffers of the host-array form (ctrl, the Jacobians); freed on every
   // return path, after the stream has finished with them (the device-pointer form has none
   // and returns without waiting for the device)
@@ -1976,6 +2217,13 @@ MJHIP_API int mjhip_inverseFDBatchEx(mjhipContext* c, int B, const mjtNum* qpos,
       FDCHECK(hipMemcpyAsync(sc, ctrl, sizeof(double)*(size_t)B*m.nu, hipMemcpyHostToDevice,
                              c->stream), "ctrl upload");
       dc = sc;
+    }
+    if (dact) {
+      double* sact = tmp.alloc((size_t)B*m.na);
+      if (!sact) { set_error("hipMalloc(act) failed"); return MJHIP_ERR_HIP; }
+      FDCHECK(hipMemcpyAsync(sact, act, sizeof(double)*(size_t)B*m.na, hipMemcpyHostToDevice,
+                             c->stream), "act upload");
+      dact = sact;
     }
   }
   long ninst = (long)B*P;
@@ -2022,7 +2270,7 @@ MJHIP_API int mjhip_inverseFDBatchEx(mjhipContext* c, int B, const mjtNum* qpos,
   const long nexp = layout ? nA : ninst;
   hipLaunchKernelGGL(k_fd_expand, dim3((unsigned)((nexp + 63)/64)), dim3(64*kExpandWaves), 0,
                      c->stream, c->dmodel, c->mirror, B, dq, dv, da, (m.nu ? dc : nullptr),
-                     eps, layout, layout ? c->fdflag : nullptr, (long)0, nexp, 0);
+                     dact, eps, layout, layout ? c->fdflag : nullptr, (long)0, nexp, 0);
   FDCHECK(hipGetLastError(), "k_fd_expand launch");
   // MJHIP_FD_FUSED=1: layout 1 in one launch (k_fdall) -- measured slower than the two
   // launches (config 5: 4.81M against 5.13M Jacobian sets/s on one box), kept for
@@ -2087,7 +2335,7 @@ MJHIP_API int mjhip_inverseFDBatchEx(mjhipContext* c, int B, const mjtNum* qpos,
       const long gblk = (ninst - nA + 63)/64;
       hipLaunchKernelGGL(k_fd_expand, dim3((unsigned)(gblk < 256 ? gblk : 256)), dim3(64), 0,
                          c->stream, c->dmodel, c->mirror, B, dq, dv, da,
-                         (m.nu ? dc : nullptr), eps, layout, c->fdflag, nA, ninst, 1);
+                         (m.nu ? dc : nullptr), dact, eps, layout, c->fdflag, nA, ninst, 1);
       FDCHECK(hipGetLastError(), "k_fd_expand (fall-back) launch");
       rc = launch_inverse(c, (int)(ninst - nA), nullptr, nullptr, nullptr, nullptr,
                           mjhipSTAGE_NONE, nullptr, 0, skipsensor, c->fdflag + 1);
@@ -2151,6 +2399,22 @@ MJHIP_API int mjhip_inverseFDBatchEx(mjhipContext* c, int B, const mjtNum* qpos,
   }
 #undef FDCHECK
   return MJHIP_OK;
+}
+
+MJHIP_API int mjhip_inverseFDBatchEx(mjhipContext* c, int B, const mjtNum* qpos,
+                                     const mjtNum* qvel, const mjtNum* qacc, const mjtNum* ctrl,
+                                     mjtNum eps, int flg_actuation, mjtNum* DfDq, mjtNum* DfDv,
+                                     mjtNum* DfDa, mjtNum* DsDq, mjtNum* DsDv, mjtNum* DsDa,
+                                     mjtNum* DmDq, int flags) {
+  if (c && flg_actuation) {
+    if (const char* why = actuation_stateless(c->hmodel)) {
+      set_error("mjhip_inverseFDBatch(flg_actuation): %s is not supported "
+                "(mjhip_inverseFDBatchAct takes act)", why);
+      return MJHIP_ERR_MODEL;
+    }
+  }
+  return mjhip_inverseFDBatchAct(c, B, qpos, qvel, qacc, ctrl, nullptr, eps, flg_actuation,
+                                 DfDq, DfDv, DfDa, DsDq, DsDv, DsDa, DmDq, flags);
 }
 
 MJHIP_API int mjhip_inverseFDBatch(mjhipContext* c, int B, const mjtNum* qpos,
@@ -2448,6 +2712,25 @@ static int get_rows(mjhipContext* c, const mjhipModel* m, mjhipData* d, int lo, 
   return rc;
 }
 
+// 1 when mj_inverseSkip reads mjData.act: mj_discreteAcc under the implicit or implicitfast
+// integrator forms qDeriv, and mjd_actuator_vel (engine_derivative.c:855-863) multiplies a
+// stateful actuator's velocity gain (affine, or a muscle's) by act
+static bool inverse_reads_act(const mjhipModel* m) {
+  if (!(m->opt.enableflags & mjhipENBL_INVDISCRETE) || !m->na ||
+      (m->opt.disableflags & mjhipDSBL_ACTUATION) ||
+      (m->opt.integrator != mjhipINT_IMPLICIT && m->opt.integrator != mjhipINT_IMPLICITFAST)) {
+    return false;
+  }
+  for (int i = 0; i < m->nu; i++) {
+    if (m->actuator_dyntype[i] == mjhipDYN_NONE) continue;
+    if (m->actuator_gaintype[i] == mjhipGAIN_MUSCLE ||
+        (m->actuator_gaintype[i] == mjhipGAIN_AFFINE && m->actuator_gainprm[10*i+2] != 0)) {
+      return true;
+    }
+  }
+  return false;
+}
+
 static int sync_stream(mjhipContext* c) {
   HIPCHECK(hipStreamSynchronize(c->stream));
   return MJHIP_OK;
@@ -2499,6 +2782,15 @@ MJHIP_API void mjhip_inverseSkip(const mjhipModel* m, mjhipData* d, int skipstag
                                             (const double*)d->actuator_force, (long)m->nu);
     if (!rc && d->qfrc_actuator) rc = put0(c, c->mirror.qfrc_actuator,
                                            (const double*)d->qfrc_actuator, (long)m->nv);
+  }
+  if (!rc && inverse_reads_act(m)) {
+    if (!d->act) {
+      set_error("the model's implicit mj_discreteAcc reads mjData.act (na = %d), but "
+                "mjhipData.act is NULL", m->na);
+      rc = MJHIP_ERR_ARG;
+    } else {
+      rc = put0(c, c->mirror.act, (const double*)d->act, (long)m->na);
+    }
   }
   if (!rc && (skipstage < mjhipSTAGE_NONE || skipstage > mjhipSTAGE_VEL)) {
     set_error("skipstage must be mjSTAGE_NONE, mjSTAGE_POS or mjSTAGE_VEL");
@@ -2663,7 +2955,7 @@ MJHIP_API void mjhip_compareFwdInv(const mjhipModel* m, mjhipData* d) {
 }
 
 // mjd_inverseFD (engine_derivative_fd.c:611-719, mujoco.h:1244-1247) for one mjData: the
-// batched FD with one base state (d's qpos, qvel, qacc, ctrl). Like the reference, d is left
+// batched FD with one base state (d's qpos, qvel, qacc, ctrl, act). Like the reference, d is left
 // with the outputs of the last evaluation (the last qpos perturbation) and its own qpos.
 MJHIP_API void mjhip_inverseFD(const mjhipModel* m, mjhipData* d, mjtNum eps,
                                mjtByte flg_actuation, mjtNum* DfDq, mjtNum* DfDv, mjtNum* DfDa,
@@ -2678,9 +2970,13 @@ MJHIP_API void mjhip_inverseFD(const mjhipModel* m, mjhipData* d, mjtNum eps,
     std::vector<double> t(P, d->time);                    // clock sensors of every evaluation
     rc = mjhip_mirrorUpload(c, "time", 0, P, t.data());
   }
-  if (!rc) rc = mjhip_inverseFDBatchEx(c, 1, d->qpos, d->qvel, d->qacc, d->ctrl, eps,
-                                       flg_actuation, DfDq, DfDv, DfDa, DsDq, DsDv, DsDa, DmDq,
-                                       kFlagFDFull);
+  if (!rc && m->na && !d->act && (flg_actuation || inverse_reads_act(m))) {
+    set_error("mjd_inverseFD reads mjData.act (na = %d), but mjhipData.act is NULL", m->na);
+    rc = MJHIP_ERR_ARG;
+  }
+  if (!rc) rc = mjhip_inverseFDBatchAct(c, 1, d->qpos, d->qvel, d->qacc, d->ctrl, d->act, eps,
+                                        flg_actuation, DfDq, DfDv, DfDa, DsDq, DsDv, DsDa, DmDq,
+                                        kFlagFDFull);
   if (!rc) {
     // the reference's last evaluation (engine_derivative_fd.c:646-715): the last qpos
     // perturbation, else the last qvel one, else the last qacc one, else the centre

@@ -7,6 +7,8 @@ mjModel and many states:
   InverseEngine.inverse(..., skipstage=, skipsensor=) batched mj_inverseSkip (inverse.c:197)
   InverseEngine.field(name)                           any mjData output field, per instance
   InverseEngine.inverse_fd(...)                       batched mjd_inverseFD  (derivative_fd.c:611)
+  InverseEngine.forward(..., act=)                    batched constraint-free mj_forward
+  InverseEngine.actuation(ctrl=, act=)                batched mj_fwdActuation (forward.c:276)
   mj_inverse(m, d) / mj_inverseSkip(m, d, ...)        single-instance drop-ins on host MjData
 
 Every call runs the HIP kernels; there is no CPU fallback. Importing this module on a
@@ -65,6 +67,10 @@ SIGNATURES = {
     "mjhip_inverseBatch": (ctypes.c_int, [_V, ctypes.c_int, _V, _V, _V, _V, ctypes.c_int,
                                           ctypes.c_int, ctypes.c_int, _I]),
     "mjhip_forwardBatch": (ctypes.c_int, [_V, ctypes.c_int, _V, _V, _V, _V, ctypes.c_int, _I]),
+    "mjhip_forwardBatchEx": (ctypes.c_int, [_V, ctypes.c_int, _V, _V, _V, _V, _V, _V, _V,
+                                            ctypes.c_int, _I]),
+    "mjhip_actuationBatch": (ctypes.c_int, [_V, ctypes.c_int, _V, _V, _V, _V, _V, ctypes.c_int,
+                                            _I]),
     "mjhip_mirrorDownload": (ctypes.c_int, [_V, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
                                             _D]),
     "mjhip_mirrorUpload": (ctypes.c_int, [_V, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
@@ -80,6 +86,9 @@ SIGNATURES = {
     "mjhip_inverseFDBatchEx": (ctypes.c_int, [_V, ctypes.c_int, _V, _V, _V, _V,
                                               ctypes.c_double, ctypes.c_int, _V, _V, _V, _V,
                                               _V, _V, _V, ctypes.c_int]),
+    "mjhip_inverseFDBatchAct": (ctypes.c_int, [_V, ctypes.c_int, _V, _V, _V, _V, _V,
+                                               ctypes.c_double, ctypes.c_int, _V, _V, _V, _V,
+                                               _V, _V, _V, ctypes.c_int]),
     "mjhip_modelCapacity": (ctypes.c_int, [_V, _I, _I]),
     "mjhip_ccdBatch": (ctypes.c_int, [_V, ctypes.c_int, _I, _I, _D, _D, _D, _D, _D,
                                       ctypes.c_int, ctypes.c_double, ctypes.c_int,
@@ -334,8 +343,13 @@ class InverseEngine:
     return out
 
   def forward(self, qpos, qvel, ctrl=None, qfrc_applied=None, xfrc_applied=None, out=None,
-              status=False):
+              status=False, act=None, activation=False):
     """Batched constraint-free mj_forward (host numpy arrays). Returns qacc [B, nv].
+
+    act [B, na]: the activations of stateful actuators (None: the mirror's, zero after
+    creation), which routes the call through mjhip_forwardBatchEx; models with activation
+    dynamics or muscles need it. activation=True also returns (act_dot, act_next) [B, na],
+    after qacc: mj_fwdActuation's act_dot and the activation mj_advance would integrate to.
 
     qfrc_applied [B, nv] / xfrc_applied [B, nbody, 6] are placed in the mirror first (they
     stay there for later calls, as in mjData); instances with constraint rows are flagged
@@ -355,10 +369,54 @@ class InverseEngine:
     if out is None:
       out = np.zeros((B, self.nv))
     st = np.zeros(B, dtype=np.int32)
-    rc = L.mjhip_forwardBatch(self.ctx, B, qpos.ctypes.data, qvel.ctypes.data, pc,
-                              out.ctypes.data, 0, st.ctypes.data_as(_I))
-    _check(rc, "mjhip_forwardBatch")     # per-instance flags come back in `st`
-    return (out, st) if status else out
+    if act is None and not activation:
+      rc = L.mjhip_forwardBatch(self.ctx, B, qpos.ctypes.data, qvel.ctypes.data, pc,
+                                out.ctypes.data, 0, st.ctypes.data_as(_I))
+      _check(rc, "mjhip_forwardBatch")     # per-instance flags come back in `st`
+      return (out, st) if status else out
+    na = self.m.na
+    pa = None
+    if act is not None and na:
+      act = np.ascontiguousarray(act, dtype=np.float64).reshape(B, na)
+      pa = act.ctypes.data
+    dot, nxt = np.zeros((B, na)), np.zeros((B, na))
+    want = activation and na
+    rc = L.mjhip_forwardBatchEx(self.ctx, B, qpos.ctypes.data, qvel.ctypes.data, pc, pa,
+                                out.ctypes.data, dot.ctypes.data if want else None,
+                                nxt.ctypes.data if want else None, 0, st.ctypes.data_as(_I))
+    _check(rc, "mjhip_forwardBatchEx")
+    res = (out,) + ((dot, nxt) if activation else ()) + ((st,) if status else ())
+    return res[0] if len(res) == 1 else res
+
+  def actuation(self, B=None, ctrl=None, act=None, status=False):
+    """Batched mj_fwdActuation over the actuator_length, actuator_velocity and
+    actuator_moment the last call left in the mirror (host numpy arrays): the call to make
+    after inverse() on a muscle-driven model. ctrl [B, nu] / act [B, na]: None uses the
+    mirror's values (then pass B). Returns (qfrc_actuator [B, nv], act_dot [B, na],
+    act_next [B, na]); actuator_force is field("actuator_force"). act is not changed."""
+    nu, na = self.m.nu, self.m.na
+    pc = pa = None
+    if ctrl is not None and nu:
+      ctrl = np.ascontiguousarray(ctrl, dtype=np.float64).reshape(-1, nu)
+      B = ctrl.shape[0] if B is None else B
+      if ctrl.shape[0] != B:
+        raise MJHIPError(f"actuation: ctrl holds {ctrl.shape[0]} rows, expected {B}")
+      pc = ctrl.ctypes.data
+    if act is not None and na:
+      act = np.ascontiguousarray(act, dtype=np.float64).reshape(-1, na)
+      B = act.shape[0] if B is None else B
+      if act.shape[0] != B:
+        raise MJHIPError(f"actuation: act holds {act.shape[0]} rows, expected {B}")
+      pa = act.ctypes.data
+    if B is None:
+      raise MJHIPError("actuation: pass B when ctrl and act come from the mirror")
+    qfrc, dot, nxt = np.zeros((B, self.nv)), np.zeros((B, na)), np.zeros((B, na))
+    st = np.zeros(B, dtype=np.int32)
+    rc = lib().mjhip_actuationBatch(self.ctx, B, pc, pa, dot.ctypes.data if na else None,
+                                    nxt.ctypes.data if na else None, qfrc.ctypes.data, 0,
+                                    st.ctypes.data_as(_I))
+    _check(rc, "mjhip_actuationBatch")
+    return (qfrc, dot, nxt, st) if status else (qfrc, dot, nxt)
 
   def field(self, name, first=0, count=None):
     """Mirror field `name` of instances [first, first+count) as [count, size] (numpy)."""
@@ -442,10 +500,12 @@ class InverseEngine:
     return ms.value
 
   def inverse_fd(self, qpos, qvel, qacc, eps=1e-6, dmdq=False, sensors=False, out=None,
-                 ctrl=None, flg_actuation=False):
+                 ctrl=None, flg_actuation=False, act=None):
     """Batched mjd_inverseFD: DfDq, DfDv, DfDa [B, nv, nv], DmDq [B, nv, nM] (or None), plus
     (DsDq, DsDv, DsDa) [B, nv, nsensordata] when sensors. With flg_actuation the forces are
-    qfrc_inverse - qfrc_actuator of the base states' controls ctrl [B, nu].
+    qfrc_inverse - qfrc_actuator of the base states' controls ctrl [B, nu] and, for
+    actuators with activation dynamics or muscles, activations act [B, na] (which routes the
+    call through mjhip_inverseFDBatchAct).
 
     Host arrays in -> numpy arrays out (PCIe both ways). Contiguous float64 torch tensors on
     the context's GPU in -> torch tensors out on that GPU, asynchronous on the context's
@@ -463,6 +523,8 @@ class InverseEngine:
         raise MJHIPError(f"inverse_fd: ctrl must hold B x nu = {B * self.m.nu} values")
       if flg_actuation and self.m.nu and ctrl is None:
         raise MJHIPError("inverse_fd: flg_actuation needs ctrl [B, nu]")
+      if act is not None and act.numel() != B * self.m.na:
+        raise MJHIPError(f"inverse_fd: act must hold B x na = {B * self.m.na} values")
       if out is None:
         mk = lambda n: torch.empty((B, nv, n), dtype=torch.float64, device=qpos.device)
         out = (mk(nv), mk(nv), mk(nv), mk(self.m.nM) if dmdq else None)
@@ -471,12 +533,19 @@ class InverseEngine:
       ptr = lambda t: None if t is None else _dptr(t)
       Ds = out[4] if len(out) > 4 else (None, None, None)
       with _TorchOrder(self):
-        rc = lib().mjhip_inverseFDBatchEx(self.ctx, B, _dptr(qpos), _dptr(qvel), _dptr(qacc),
-                                          None if ctrl is None else _dptr(ctrl), eps,
-                                          int(bool(flg_actuation)), ptr(out[0]), ptr(out[1]),
-                                          ptr(out[2]), *map(ptr, Ds), ptr(out[3]),
-                                          FLAG_DEVICE_PTRS)
-      _check(rc, "mjhip_inverseFDBatchEx")
+        if act is None:
+          rc = lib().mjhip_inverseFDBatchEx(self.ctx, B, _dptr(qpos), _dptr(qvel), _dptr(qacc),
+                                            None if ctrl is None else _dptr(ctrl), eps,
+                                            int(bool(flg_actuation)), ptr(out[0]), ptr(out[1]),
+                                            ptr(out[2]), *map(ptr, Ds), ptr(out[3]),
+                                            FLAG_DEVICE_PTRS)
+        else:
+          rc = lib().mjhip_inverseFDBatchAct(self.ctx, B, _dptr(qpos), _dptr(qvel),
+                                             _dptr(qacc), None if ctrl is None else _dptr(ctrl),
+                                             _dptr(act), eps, int(bool(flg_actuation)),
+                                             ptr(out[0]), ptr(out[1]), ptr(out[2]),
+                                             *map(ptr, Ds), ptr(out[3]), FLAG_DEVICE_PTRS)
+      _check(rc, "mjhip_inverseFDBatchEx" if act is None else "mjhip_inverseFDBatchAct")
       return tuple(out)
     qpos = np.ascontiguousarray(qpos, dtype=np.float64).reshape(-1, self.nq)
     qvel = np.ascontiguousarray(qvel, dtype=np.float64).reshape(-1, self.nv)
@@ -490,11 +559,22 @@ class InverseEngine:
     p = lambda a: None if a is None else a.ctypes.data
     if ctrl is not None:
       ctrl = np.ascontiguousarray(ctrl, dtype=np.float64).reshape(B, -1)
-    _check(lib().mjhip_inverseFDBatchEx(self.ctx, B, qpos.ctypes.data, qvel.ctypes.data,
-                                        qacc.ctypes.data, p(ctrl), eps,
-                                        int(bool(flg_actuation)), p(DfDq), p(DfDv), p(DfDa),
-                                        *map(p, Ds), p(DmDq), 0),
-           "mjhip_inverseFDBatchEx")
+    if act is None:
+      _check(lib().mjhip_inverseFDBatchEx(self.ctx, B, qpos.ctypes.data, qvel.ctypes.data,
+                                          qacc.ctypes.data, p(ctrl), eps,
+                                          int(bool(flg_actuation)), p(DfDq), p(DfDv), p(DfDa),
+                                          *map(p, Ds), p(DmDq), 0),
+             "mjhip_inverseFDBatchEx")
+    else:
+      act = np.ascontiguousarray(act, dtype=np.float64).reshape(B, -1)
+      if act.shape[1] != self.m.na:
+        raise MJHIPError(f"inverse_fd: act must be [B, na] = [{B}, {self.m.na}]")
+      _check(lib().mjhip_inverseFDBatchAct(self.ctx, B, qpos.ctypes.data, qvel.ctypes.data,
+                                           qacc.ctypes.data, p(ctrl),
+                                           act.ctypes.data if self.m.na else None, eps,
+                                           int(bool(flg_actuation)), p(DfDq), p(DfDv), p(DfDa),
+                                           *map(p, Ds), p(DmDq), 0),
+             "mjhip_inverseFDBatchAct")
     if sensors:
       return DfDq, DfDv, DfDa, DmDq, Ds
     return DfDq, DfDv, DfDa, DmDq

@@ -64,7 +64,7 @@ def _parse():
   text = open(FIELDS_HEADER).read()
   sizes = re.findall(r"XS\((\w+)\)", _macro_body(text, "MJHIP_MODEL_SIZES"))
   model = []
-  for group in ("MJHIP_MODEL_POINTERS_M", "MJHIP_MODEL_POINTERS_D"):
+  for group in ("MJHIP_MODEL_POINTERS_M", "MJHIP_MODEL_POINTERS_D", "MJHIP_MODEL_POINTERS_A"):
     for ct, nm, d0, d1 in re.findall(
         r"X\(\s*(\w+)\s*,\s*(\w+)\s*,\s*(\w+)\s*,\s*([\w()]+)\s*\)",
         _macro_body(text, group)):
@@ -85,7 +85,8 @@ def _parse():
   sparse = [SparseField(ct, nm, dim) for ct, nm, dim in re.findall(
       r"XJ\(\s*(\w+)\s*,\s*(\w+)\s*,\s*(\w+)\s*\)", _macro_body(text, "MJHIP_DATA_SPARSE"))]
   return (sizes, model, data, xd("MJHIP_DATA_FORWARD"), xd("MJHIP_DATA_SENSOR_AUX"),
-          rows("MJHIP_DATA_EFC", "XE"), rows("MJHIP_DATA_CONTACT", "XC"), sparse)
+          rows("MJHIP_DATA_EFC", "XE"), rows("MJHIP_DATA_CONTACT", "XC"), sparse,
+          xd("MJHIP_DATA_ACTIVATION"))
 
 
 @dataclass(frozen=True)
@@ -114,9 +115,12 @@ class SparseField:
 
 
 (MODEL_SIZES, MODEL_FIELDS, DATA_FIELDS, FORWARD_FIELDS, AUX_FIELDS, EFC_FIELDS,
- CONTACT_FIELDS, SPARSE_FIELDS) = _parse()
+ CONTACT_FIELDS, SPARSE_FIELDS, ACT_FIELDS) = _parse()
 MODEL_FIELD = {f.name: f for f in MODEL_FIELDS}
-DATA_FIELD = {f.name: f for f in DATA_FIELDS + FORWARD_FIELDS + AUX_FIELDS}
+ACTIVATION_MODEL_FIELDS = frozenset(n for n in MODEL_FIELD if n in (
+    "actuator_actadr", "actuator_actnum", "actuator_actlimited", "actuator_actearly",
+    "actuator_actrange", "actuator_lengthrange"))
+DATA_FIELD = {f.name: f for f in DATA_FIELDS + FORWARD_FIELDS + AUX_FIELDS + ACT_FIELDS}
 
 
 class Option(ctypes.Structure):
@@ -159,7 +163,8 @@ class CData(ctypes.Structure):
                                            "ncon")] +
               [(f.name, ctypes.POINTER(CTYPE[f.ctype])) for f in EFC_FIELDS + CONTACT_FIELDS] +
               [("nJ", ctypes.c_int)] +
-              [(f.name, ctypes.POINTER(CTYPE[f.ctype])) for f in SPARSE_FIELDS])
+              [(f.name, ctypes.POINTER(CTYPE[f.ctype])) for f in SPARSE_FIELDS] +
+              [(f.name, ctypes.POINTER(ctypes.c_double)) for f in ACT_FIELDS])
 
 
 def is_sparse(m) -> bool:
@@ -210,6 +215,16 @@ def model_signature(m) -> int:
     feed(np.int32(o[k]).tobytes())
   feed(np.float64(o.get("ccd_tolerance", 1e-6)).tobytes())
   feed(np.int32(o.get("ccd_iterations", 50)).tobytes())
+  uses_act = model_uses_activation(m)
   for f in MODEL_FIELDS:
+    if f.name in ACTIVATION_MODEL_FIELDS and not uses_act:
+      continue                 # not read for such a model (mjhip_modelUsesActivation)
     feed(np.ascontiguousarray(getattr(m, f.name), dtype=NPTYPE[f.ctype]).tobytes())
   return h
+
+
+def model_uses_activation(m) -> bool:
+  """mjhip_modelUsesActivation (csrc/mjhip.hip): the model has activation states or a muscle
+  gain / bias, so the arrays of MJHIP_MODEL_POINTERS_A are read."""
+  return bool(m.sizes.get("na", 0) > 0 or np.any(np.asarray(m.actuator_gaintype) == 2) or
+              np.any(np.asarray(m.actuator_biastype) == 2))

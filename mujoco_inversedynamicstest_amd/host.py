@@ -60,7 +60,8 @@ class MjData:
     self.m = m
     sizes = m.sizes
     self._arrays = {}
-    for f in fields.DATA_FIELDS + fields.FORWARD_FIELDS + fields.AUX_FIELDS:
+    for f in (fields.DATA_FIELDS + fields.FORWARD_FIELDS + fields.AUX_FIELDS +
+              fields.ACT_FIELDS):             # act = 0, as mj_resetData leaves it
       n = f.size(sizes)
       self._arrays[f.name] = np.zeros(max(n, 1))
     if efc_capacity is None or con_capacity is None:

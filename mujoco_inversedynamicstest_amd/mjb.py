@@ -450,13 +450,14 @@ def unsupported(ints, arrays) -> str | None:
   if ints["nwrap"] and not np.isin(arrays["wrap_type"], (1, 2, 3, 4, 5)).all():
     return "unknown tendon wrap object type"
   if ints["nu"]:
-    dyn = np.asarray(arrays["actuator_dyntype"]).reshape(-1)
     gain = np.asarray(arrays["actuator_gaintype"]).reshape(-1)
-    kv = np.asarray(arrays["actuator_gainprm"]).reshape(ints["nu"], -1)[:, 2]
-    if np.any((dyn != 0) & (gain == 1) & (kv != 0)):
-      return "an affine velocity gain with activation dynamics (reads mjData.act)"
-    if np.any(gain >= 2) or np.any(np.asarray(arrays["actuator_biastype"]) >= 2):
-      return "muscle or user actuator gain/bias"
+    if np.any(gain >= 3) or np.any(np.asarray(arrays["actuator_biastype"]) >= 3):
+      return "user actuator gain/bias"
+    # the device indexes act by these: every activation must lie inside [0, na)
+    adr = np.asarray(arrays["actuator_actadr"]).reshape(-1)
+    num = np.asarray(arrays["actuator_actnum"]).reshape(-1)
+    if np.any((adr < -1) | (num < 0) | ((adr >= 0) & ((num < 1) | (adr + num > ints["na"])))):
+      return "activation addresses outside mjData.act"
   if ints["ngeom"] and np.any(np.asarray(arrays["geom_type"]) == 8):
     return "SDF geoms"
   return None
@@ -538,17 +539,7 @@ def write(m) -> bytes:
   ints["nnames"] = len(names)
   ints["npaths"] = 0
   ints["nnames_map"] = 0
-  nu = ints["nu"]
-  dyn = np.asarray(getattr(m, "actuator_dyntype")).reshape(-1) if nu else np.zeros(0)
-  actadr = np.full(nu, -1, np.int32)
-  actnum = np.zeros(nu, np.int32)
-  k = 0
-  for i in range(nu):
-    if dyn[i]:
-      actadr[i], actnum[i] = k, 1
-      k += 1
-  extra = {"names": np.frombuffer(names, dtype=np.uint8), "actuator_actadr": actadr,
-           "actuator_actnum": actnum, **adrs}
+  extra = {"names": np.frombuffer(names, dtype=np.uint8), **adrs}
   out = [struct.pack(f"<{NHEADER}i", *header()),
          struct.pack(f"<{len(INTS)}i", *[ints[k] for k in INTS]),
          struct.pack("<QQ", 1 << 24, buffer_size(ints))]

@@ -359,7 +359,8 @@ class _Defaults:
     return out
 
 
-ACTUATOR_TAGS = ("general", "motor", "position", "velocity", "intvelocity", "adhesion")
+ACTUATOR_TAGS = ("general", "motor", "position", "velocity", "intvelocity", "adhesion",
+                 "muscle")
 
 # name references of the referencing elements an <attach>/<replicate> namespaces (attribute
 # -> kind of object it names; mjCEquality/mjCActuator/mjCSensor::NameSpace,
@@ -559,7 +560,25 @@ class Model:
         fill = -1 if f.name == "geom_dataid" or f.name == "mesh_graphadr" else 0
         a = np.full(shape if shape[1] != 1 else shape[:1], fill, dtype=fields.NPTYPE[f.ctype])
         setattr(m, f.name, a)
+    if "actuator_actadr" not in z.files or "actuator_actnum" not in z.files:
+      # a file from before activations were carried: the compiler's addresses (zeros would
+      # alias every actuator to act[0])
+      m.actuator_actadr, m.actuator_actnum = activation_addresses(m.actuator_dyntype)
     return m
+
+
+def activation_addresses(dyntype):
+  """(actuator_actadr, actuator_actnum) as the compiler assigns them (user_model.cc): -1 / 0
+  for dyntype none, otherwise consecutive addresses with one activation each."""
+  dyn = np.asarray(dyntype).reshape(-1)
+  adr = np.full(dyn.size, -1, np.int32)
+  num = np.zeros(dyn.size, np.int32)
+  k = 0
+  for i in range(dyn.size):
+    if dyn[i]:
+      adr[i], num[i] = k, 1
+      k += 1
+  return adr, num
 
 
 _NAME_SIZE = {"body": "nbody", "jnt": "njnt", "geom": "ngeom", "site": "nsite", "cam": "ncam",
@@ -1991,6 +2010,10 @@ class MJCFCompiler:
     acrank = arr("actuator_cranklength", nu, np.float64)
     arr("actuator_length0", nu, np.float64)
     arr("actuator_acc0", nu, np.float64)
+    aactl = arr("actuator_actlimited", nu, np.uint8)
+    aearly = arr("actuator_actearly", nu, np.uint8)
+    aactr = arr("actuator_actrange", (nu, 2), np.float64)
+    alenr = arr("actuator_lengthrange", (nu, 2), np.float64)
     na_count = 0                        # activation states (dyntype != none)
     for ai, a in enumerate(self.actuators):
       tag = a["__tag"]
@@ -2038,17 +2061,22 @@ class MJCFCompiler:
         if "biasprm" in a:
           v = _floats(a["biasprm"])
           abiasprm[ai, :len(v)] = v
-        again[ai] = {"fixed": 0, "affine": 1}[a.get("gaintype", "fixed")]
-        abias[ai] = {"none": 0, "affine": 1}[a.get("biastype", "none")]
+        gt, bt = a.get("gaintype", "fixed"), a.get("biastype", "none")
+        if gt not in ("fixed", "affine", "muscle"):
+          raise MJCFError(f"actuator gaintype '{gt}' is not in the supported subset")
+        if bt not in ("none", "affine", "muscle"):
+          raise MJCFError(f"actuator biastype '{bt}' is not in the supported subset")
+        again[ai] = {"fixed": 0, "affine": 1, "muscle": 2}[gt]
+        abias[ai] = {"none": 0, "affine": 1, "muscle": 2}[bt]
         dyn = a.get("dyntype", "none")
-        if dyn not in ("none", "integrator", "filter", "filterexact"):
+        if dyn not in ("none", "integrator", "filter", "filterexact", "muscle"):
           raise MJCFError(f"actuator dyntype '{dyn}' is not in the supported subset")
-        adyn[ai] = {"none": 0, "integrator": 1, "filter": 2, "filterexact": 3}[dyn]
-        if adyn[ai] and again[ai] == 1 and againprm[ai, 2] != 0:
-          # mjd_actuator_vel (engine_derivative.c:855-863) multiplies the velocity gain by
-          # mjData.act[last] for such an actuator; act is not an input of this path
-          raise MJCFError("an affine velocity gain with activation dynamics is not in the "
-                          "supported subset")
+        adyn[ai] = {"none": 0, "integrator": 1, "filter": 2, "filterexact": 3, "muscle": 4}[dyn]
+        aearly[ai] = a.get("actearly", "false") == "true"
+        if "actdim" in a and int(a["actdim"]) != (adyn[ai] != 0):
+          # user_objects.cc:6012-6023: actdim > 1 needs dyntype user; 1 / 0 must match dyntype
+          raise MJCFError("actuator actdim other than one activation per stateful actuator "
+                          "is not in the supported subset")
         if "dynprm" in a:
           v = _floats(a["dynprm"])
           adynprm[ai, :len(v)] = v
@@ -2106,6 +2134,25 @@ class MJCFCompiler:
         abiasprm[ai, 1] = -kp
         abiasprm[ai, 2] = -kv
         na_count += 1
+      elif tag == "muscle":             # xml_native_reader.cc:2301-2338
+        adynprm[ai, :2] = 0.01, 0.04     # tau act, tau deact
+        againprm[ai, :9] = 0.75, 1.05, -1, 200, 0.5, 1.6, 1.5, 1.3, 1.2
+        if "timeconst" in a:
+          v = _floats(a["timeconst"])
+          adynprm[ai, :len(v)] = v
+        if "tausmooth" in a:
+          adynprm[ai, 2] = float(a["tausmooth"])
+          if adynprm[ai, 2] < 0:
+            raise MJCFError("muscle tausmooth cannot be negative")
+        if "range" in a:
+          v = _floats(a["range"])
+          againprm[ai, :len(v)] = v
+        for k, key in enumerate(("force", "scale", "lmin", "lmax", "vmax", "fpmax", "fvmax")):
+          if key in a:
+            againprm[ai, 2 + k] = float(a[key])
+        abiasprm[ai, :9] = againprm[ai, :9]      # biasprm = gainprm
+        adyn[ai], again[ai], abias[ai] = 4, 2, 2
+        na_count += 1
       elif tag == "adhesion":           # xml_native_reader.cc:2341-2356
         againprm[ai, 0] = float(a.get("gain", 1.0))
         if againprm[ai, 0] < 0:
@@ -2122,6 +2169,26 @@ class MJCFCompiler:
       fl = a.get("forcelimited", "auto")
       afl[ai] = (not (fr[0] == 0 and fr[1] == 0)) if fl == "auto" else (fl == "true")
       afr[ai] = fr
+      # actlimited / actrange as ctrllimited / ctrlrange (user_objects.cc:5993-6010)
+      ar = _floats(a["actrange"]) if "actrange" in a else [0.0, 0.0]
+      al = a.get("actlimited", "auto")
+      aactl[ai] = (not (ar[0] == 0 and ar[1] == 0)) if al == "auto" else (al == "true")
+      if tag == "intvelocity" and ar[0] < ar[1]:
+        aactl[ai] = 1                   # xml_native_reader.cc:2239-2242
+      aactr[ai] = ar
+      if aactl[ai] and ar[0] >= ar[1]:
+        raise MJCFError("invalid actrange for actuator")
+      if aactl[ai] and not adyn[ai]:
+        raise MJCFError("actrange specified but dyntype is 'none' in actuator")
+      if "lengthrange" in a:
+        alenr[ai] = _floats(a["lengthrange"])
+      if (again[ai] == 2 or abias[ai] == 2) and not alenr[ai, 0] < alenr[ai, 1]:
+        # mj_setLengthRange (engine_setconst.c:639-666) keeps an existing range (mjLROpt
+        # useexisting, engine_io.c:78-81) and otherwise finds one by simulation
+        raise MJCFError("a muscle gain or bias needs an explicit lengthrange with "
+                        "lengthrange[0] < lengthrange[1]: computing it by simulation "
+                        "(mj_setLengthRange) is not in the supported subset")
+    A["actuator_actadr"], A["actuator_actnum"] = activation_addresses(adyn)
     # equality constraints (xml_native_reader.cc:1898-2035, user_objects.cc:5139-5220;
     # eq_data defaults mjs_defaultEquality user_init.c:312-319; missing body-constraint
     # data are filled by setconst.py as mj_setConst does, engine_setconst.c:289-340)
