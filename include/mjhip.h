@@ -420,6 +420,67 @@ MJHIP_API int mjhip_actuationBatch(mjhipContext* c, int B, const mjtNum* ctrl,
                                    const mjtNum* act, mjtNum* act_dot, mjtNum* act_next,
                                    mjtNum* qfrc_actuator, int flags, int* status);
 
+/* Batched rollout: nstep calls of mj_step (engine_forward.c:1134-1168) per instance in one
+ * launch, for constraint-free states (the set mjhip_forwardBatch covers). nstep = 1 is
+ * mj_step. Every integrator is carried: Euler (mj_EulerSkip, with mjDSBL_EULERDAMP), RK4
+ * (mj_RungeKutta, activations included), implicitfast and implicit (mj_implicitSkip).
+ * Sensors and energy are not computed (skipsensor = 1 throughout) and time is not carried.
+ *
+ * Inputs (mjhipRolloutIn): the initial qpos / qvel (B x nq, B x nv) and optional act
+ * (B x na), row-major, unless MJHIP_FLAG_MIRROR_INPUT (the mirror's state is advanced); ctrl
+ * (n = nu), qfrc_applied (n = nv) and xfrc_applied (n = 6 nbody), each with a mode:
+ * MJHIP_ROLLOUT_ABSENT (the mirror's value), MJHIP_ROLLOUT_HELD (B x n, one row per
+ * instance) or MJHIP_ROLLOUT_PERSTEP (B x nstep x n). Outputs (mjhipRolloutOut), all
+ * optional: state (B x nstep x (nq+nv+na), the state after each step), qacc (B x nstep x nv,
+ * the first mj_forward's qacc of each step), fwdinv (B x nstep). Host arrays, or device
+ * arrays with MJHIP_FLAG_DEVICE_PTRS. The final state is left in the mirror's qpos, qvel,
+ * act. Both structs carry their own size so that they can grow at the end.
+ *
+ * fwdinv: with MJHIP_STEP_FWDINV in flags (or mjENBL_FWDINV in the model) each step's forward
+ * is followed by mj_inverseSkip(mjSTAGE_VEL, 1) on its qacc, and fwdinv receives
+ * |qfrc_applied + qfrc_actuator + J'xfrc_applied - qfrc_inverse| (src/inverse/
+ * inverse_test.cpp:72-99; mj_compareFwdInv's second number when there are no rows).
+ *
+ * Stop rule: an instance whose step's forward reports constraint rows
+ * (MJHIP_INST_UNSUPPORTED) or a bad qpos / qvel / qacc (MJHIP_INST_BADQPOS/QVEL/QACC), in any
+ * of RK4's four evaluations, is not advanced at that step or later: its remaining state rows
+ * repeat the last good state, its remaining qacc and fwdinv rows are 0, steps_done[i] (B
+ * ints, optional) is the number of completed steps and status[i] keeps the bits. Returns
+ * MJHIP_ERR_INSTANCE when a status word is nonzero. Models mjhip_forwardBatchEx refuses are
+ * refused the same way.
+ *
+ * Side effects on the mirror: the given initial state is placed in it even when nstep = 0,
+ * and held or per-step ctrl / qfrc_applied / xfrc_applied are written into the mirror's
+ * fields of the same names, where the last values used stay after the call (as they would in
+ * mjData). With MJHIP_FLAG_DEVICE_PTRS steps_done is device memory too; status is always a
+ * host array. */
+#define MJHIP_ROLLOUT_ABSENT  0
+#define MJHIP_ROLLOUT_HELD    1
+#define MJHIP_ROLLOUT_PERSTEP 2
+#define MJHIP_STEP_FWDINV          (1 << 4)  /* mjhip_rolloutBatch: fill fwdinv */
+typedef struct mjhipRolloutIn_ {
+  int size;                      /* sizeof(mjhipRolloutIn) as the caller compiled it */
+  int ctrl_mode;                 /* MJHIP_ROLLOUT_* of ctrl, qfrc_applied, xfrc_applied */
+  int qfrc_applied_mode;
+  int xfrc_applied_mode;
+  const mjtNum* qpos;
+  const mjtNum* qvel;
+  const mjtNum* act;
+  const mjtNum* ctrl;
+  const mjtNum* qfrc_applied;
+  const mjtNum* xfrc_applied;
+} mjhipRolloutIn;
+typedef struct mjhipRolloutOut_ {
+  int size;                      /* sizeof(mjhipRolloutOut) as the caller compiled it */
+  int reserved;
+  mjtNum* state;
+  mjtNum* qacc;
+  mjtNum* fwdinv;
+} mjhipRolloutOut;
+MJHIP_API int mjhip_rolloutBatch(mjhipContext* c, int B, int nstep, const mjhipRolloutIn* in,
+                                 const mjhipRolloutOut* out, int flags, int* status,
+                                 int* steps_done);
+
 /* copy one mirror field (reference name) of instances [first, first+count) to/from host
  * memory in the reference's per-instance row-major layout (count x fieldSize) */
 MJHIP_API int mjhip_mirrorDownload(mjhipContext* c, const char* field, int first, int count,

@@ -28,6 +28,7 @@
 #include "fast_kernels.h"
 #include "kernels.h"
 #include "pair_program.h"
+#include "rollout.h"
 // lane-count variants of the cooperative kernel (kern_constraint.hip), measurement only
 extern template __global__ void k_constraint_coop<8, true, false, false>(mjhipModel, Mirror, int, const int*, const int*, const CoopPair*, const mjh::ContactParam*, const unsigned long long*, int, double*, int*, int*);
 extern template __global__ void k_constraint_coop<32, true, false, false>(mjhipModel, Mirror, int, const int*, const int*, const CoopPair*, const mjh::ContactParam*, const unsigned long long*, int, double*, int*, int*);
@@ -581,6 +582,9 @@ struct mjhipContext_ {
   mjhipTimerStat timer[mjhipNTIMER]{};
   unsigned long long traw[MJH_TSLOTS]{};   // the raw mark sums (tools/exp_phases.py)
   hipEvent_t tev0 = nullptr, tev1 = nullptr;
+  // mjhip_rolloutBatch's integrator scratch (csrc/step.h), [capacity/64][k][64]: allocated by
+  // the context's first rollout, freed with the context
+  double* rollout_scratch = nullptr;
 };
 
 // 1 when the model has activation states or a muscle gain / bias: only then are the arrays
@@ -1079,6 +1083,7 @@ MJHIP_API void mjhip_contextFree(mjhipContext* c) {
   hipFree(c->cparams);
   hipFree(c->prog_ipair);
   hipFree(c->masks);
+  hipFree(c->rollout_scratch);
   hipFree(c->mirror_buf);
   hipFree(c->dmodel_buf);
   if (c->rt_module) hipModuleUnload(c->rt_module);
@@ -1926,6 +1931,163 @@ MJHIP_API int mjhip_forwardBatch(mjhipContext* c, int B, const mjtNum* qpos, con
   }
   return mjhip_forwardBatchEx(c, B, qpos, qvel, ctrl, nullptr, qacc, nullptr, nullptr, flags,
                               status);
+}
+
+// Device buffers of one host-array rollout call, released when the call returns
+struct RolloutTemps {
+  std::vector<void*> bufs;
+  ~RolloutTemps() { for (void* p : bufs) hipFree(p); }
+  double* get(size_t doubles) {
+    void* p = nullptr;
+    if (hipMalloc(&p, sizeof(double)*(doubles ? doubles : 1)) != hipSuccess) return nullptr;
+    bufs.push_back(p);
+    return (double*)p;
+  }
+};
+
+MJHIP_API int mjhip_rolloutBatch(mjhipContext* c, int B, int nstep, const mjhipRolloutIn* in,
+                                 const mjhipRolloutOut* out, int flags, int* status,
+                                 int* steps_done) {
+  if (!in || in->size < (int)sizeof(mjhipRolloutIn)) {
+    set_error("mjhip_rolloutBatch: mjhipRolloutIn is NULL or its size field (%d) is below %d",
+              in ? in->size : 0, (int)sizeof(mjhipRolloutIn));
+    return MJHIP_ERR_ARG;
+  }
+  if (!out || out->size < (int)sizeof(mjhipRolloutOut)) {
+    set_error("mjhip_rolloutBatch: mjhipRolloutOut is NULL or its size field (%d) is below %d",
+              out ? out->size : 0, (int)sizeof(mjhipRolloutOut));
+    return MJHIP_ERR_ARG;
+  }
+  if (!c) {
+    if (mjhip_deviceCount() <= 0) {
+      set_error("mjhip_rolloutBatch: no HIP device (there is no CPU fallback)");
+      return MJHIP_ERR_NO_DEVICE;
+    }
+    set_error("mjhip_rolloutBatch: NULL context");
+    return MJHIP_ERR_ARG;
+  }
+  const int modes[3] = {in->ctrl_mode, in->qfrc_applied_mode, in->xfrc_applied_mode};
+  const mjtNum* ptrs[3] = {in->ctrl, in->qfrc_applied, in->xfrc_applied};
+  for (int k = 0; k < 3; k++) {
+    if (modes[k] < MJHIP_ROLLOUT_ABSENT || modes[k] > MJHIP_ROLLOUT_PERSTEP ||
+        (modes[k] != MJHIP_ROLLOUT_ABSENT && !ptrs[k])) {
+      set_error("mjhip_rolloutBatch: input %d has mode %d and pointer %p", k, modes[k],
+                (const void*)ptrs[k]);
+      return MJHIP_ERR_ARG;
+    }
+  }
+  if (B < 0 || nstep < 0) {
+    set_error("mjhip_rolloutBatch: bad argument");
+    return MJHIP_ERR_ARG;
+  }
+  if (B > c->capacity) {
+    set_error("batch %d exceeds context capacity %d", B, c->capacity);
+    return MJHIP_ERR_CAPACITY;
+  }
+  const mjhipModel& m = c->hmodel;
+  if (const char* why = actuation_unsupported(m)) {
+    set_error("mjhip_rolloutBatch: %s is not supported", why);
+    return MJHIP_ERR_MODEL;
+  }
+  const bool dev = flags & MJHIP_FLAG_DEVICE_PTRS;
+  const bool mirror_in = flags & MJHIP_FLAG_MIRROR_INPUT;
+  if (!mirror_in && (!in->qpos || !in->qvel)) {
+    set_error("mjhip_rolloutBatch: qpos/qvel required without MJHIP_FLAG_MIRROR_INPUT");
+    return MJHIP_ERR_ARG;
+  }
+  if (B == 0) return MJHIP_OK;              // nstep = 0 still places the state in the mirror
+  HIPCHECK(hipSetDevice(c->device));
+  if (!c->rollout_scratch) {
+    const size_t n = (size_t)mjhip_rolloutScratchDoubles(&m) * c->capacity;
+    HIPCHECK(hipMalloc((void**)&c->rollout_scratch, sizeof(double)*(n ? n : 1)));
+  }
+  const size_t nB = (size_t)B, T = (size_t)nstep;
+  const size_t nin[3] = {(size_t)m.nu, (size_t)m.nv, 6*(size_t)m.nbody};
+  const size_t nstate = (size_t)m.nq + m.nv + m.na;
+  RolloutCall call{};
+  call.scratch = c->rollout_scratch;
+  call.B = B;
+  call.T = nstep;
+  call.fwdinv_on = (flags & MJHIP_STEP_FWDINV) || (m.opt.enableflags & mjhipENBL_FWDINV);
+  call.ctrl_mode = m.nu ? in->ctrl_mode : kRolloutAbsent;
+  call.qfrc_mode = in->qfrc_applied_mode;
+  call.xfrc_mode = in->xfrc_applied_mode;
+  call.status = c->status;
+  RolloutTemps tmp;
+  int* dsteps = nullptr;
+  if (dev) {
+    if (!mirror_in) {
+      call.qpos = in->qpos;
+      call.qvel = in->qvel;
+      call.act = m.na ? in->act : nullptr;
+    }
+    call.ctrl = in->ctrl;
+    call.qfrc_applied = in->qfrc_applied;
+    call.xfrc_applied = in->xfrc_applied;
+    call.state = out->state;
+    call.qacc = out->qacc;
+    call.fwdinv = out->fwdinv;
+    call.steps_done = steps_done;
+  } else {
+    auto up = [&](const mjtNum* src, size_t n) -> double* {
+      double* p = tmp.get(n);
+      if (p && hipMemcpyAsync(p, src, sizeof(double)*n, hipMemcpyHostToDevice, c->stream) !=
+                   hipSuccess) {
+        return nullptr;
+      }
+      return p;
+    };
+    bool ok = true;
+    if (!mirror_in) {
+      ok = ok && (call.qpos = up(in->qpos, nB*m.nq));
+      ok = ok && (call.qvel = up(in->qvel, nB*m.nv));
+      if (in->act && m.na) ok = ok && (call.act = up(in->act, nB*m.na));
+    }
+    const int cm[3] = {call.ctrl_mode, call.qfrc_mode, call.xfrc_mode};
+    const double** dst[3] = {&call.ctrl, &call.qfrc_applied, &call.xfrc_applied};
+    for (int k = 0; k < 3; k++) {
+      if (cm[k] == kRolloutAbsent) continue;
+      ok = ok && (*dst[k] = up(ptrs[k], nB*nin[k]*(cm[k] == kRolloutPerStep ? T : 1)));
+    }
+    if (out->state) ok = ok && (call.state = tmp.get(nB*T*nstate));
+    if (out->qacc) ok = ok && (call.qacc = tmp.get(nB*T*m.nv));
+    if (out->fwdinv) ok = ok && (call.fwdinv = tmp.get(nB*T));
+    if (steps_done) ok = ok && (dsteps = (int*)tmp.get((nB + 1)/2));
+    call.steps_done = dsteps;
+    if (!ok) {
+      set_error("mjhip_rolloutBatch: staging the host arrays on the device failed");
+      return MJHIP_ERR_HIP;
+    }
+  }
+  if (!call.fwdinv) call.fwdinv_on = 0;
+  // measurement only (tools/rollout_bench.py, the byte-equality test): MJHIP_ROLLOUT_DIRECT=1
+  // in the environment selects the per-lane row store instead of the LDS write-out
+  const char* direct_env = getenv("MJHIP_ROLLOUT_DIRECT");
+  if (mjhip_launchRollout(c->stream, c->dmodel, c->mirror, call, c->con_cap > 0,
+                          direct_env && direct_env[0] == '1')) {
+    set_error("mjhip_rolloutBatch: kernel launch failed");
+    return MJHIP_ERR_HIP;
+  }
+  if (!dev) {
+    if (out->state) {
+      HIPCHECK(hipMemcpyAsync(out->state, call.state, sizeof(double)*nB*T*nstate,
+                              hipMemcpyDeviceToHost, c->stream));
+    }
+    if (out->qacc) {
+      HIPCHECK(hipMemcpyAsync(out->qacc, call.qacc, sizeof(double)*nB*T*m.nv,
+                              hipMemcpyDeviceToHost, c->stream));
+    }
+    if (out->fwdinv) {
+      HIPCHECK(hipMemcpyAsync(out->fwdinv, call.fwdinv, sizeof(double)*nB*T,
+                              hipMemcpyDeviceToHost, c->stream));
+    }
+    if (steps_done) {
+      HIPCHECK(hipMemcpyAsync(steps_done, dsteps, sizeof(int)*nB, hipMemcpyDeviceToHost,
+                              c->stream));
+    }
+  }
+  // host arrays: collect_status synchronizes the stream before the staging buffers go
+  return collect_status(c, B, status, status || !dev);
 }
 
 MJHIP_API int mjhip_actuationBatch(mjhipContext* c, int B, const mjtNum* ctrl,

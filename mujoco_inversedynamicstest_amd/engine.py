@@ -71,6 +71,8 @@ SIGNATURES = {
                                             ctypes.c_int, _I]),
     "mjhip_actuationBatch": (ctypes.c_int, [_V, ctypes.c_int, _V, _V, _V, _V, _V, ctypes.c_int,
                                             _I]),
+    "mjhip_rolloutBatch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, _V, ctypes.c_int,
+                                          _V, _V]),
     "mjhip_mirrorDownload": (ctypes.c_int, [_V, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
                                             _D]),
     "mjhip_mirrorUpload": (ctypes.c_int, [_V, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
@@ -115,6 +117,25 @@ SIGNATURES = {
 
 class MJHIPError(RuntimeError):
   pass
+
+
+# mjhip_rolloutBatch (include/mjhip.h): input modes, flags and the two argument structs
+ROLLOUT_ABSENT, ROLLOUT_HELD, ROLLOUT_PERSTEP = 0, 1, 2
+STEP_FWDINV = 1 << 4
+
+
+class RolloutIn(ctypes.Structure):
+  """mjhipRolloutIn."""
+  _fields_ = [("size", ctypes.c_int), ("ctrl_mode", ctypes.c_int),
+              ("qfrc_applied_mode", ctypes.c_int), ("xfrc_applied_mode", ctypes.c_int),
+              ("qpos", _V), ("qvel", _V), ("act", _V), ("ctrl", _V), ("qfrc_applied", _V),
+              ("xfrc_applied", _V)]
+
+
+class RolloutOut(ctypes.Structure):
+  """mjhipRolloutOut."""
+  _fields_ = [("size", ctypes.c_int), ("reserved", ctypes.c_int), ("state", _V), ("qacc", _V),
+              ("fwdinv", _V)]
 
 
 # the reference's mjtTimer slots (include/mujoco/mjdata.h), mjhipTimer in include/mjhip.h
@@ -387,6 +408,78 @@ class InverseEngine:
     _check(rc, "mjhip_forwardBatchEx")
     res = (out,) + ((dot, nxt) if activation else ()) + ((st,) if status else ())
     return res[0] if len(res) == 1 else res
+
+  def rollout(self, qpos, qvel, nstep, act=None, ctrl=None, qfrc_applied=None,
+              xfrc_applied=None, state=True, qacc=False, fwdinv=False, status=False):
+    """nstep calls of mj_step per instance in one launch (mjhip_rolloutBatch; host numpy
+    arrays), for constraint-free states. qpos [B, nq], qvel [B, nv], act [B, na] (None: the
+    mirror's). ctrl / qfrc_applied / xfrc_applied: None (the mirror's values), one row per
+    instance ([B, n], held for every step) or per step ([B, nstep, n]); n = nu, nv, 6 nbody.
+
+    Returns, in this order, those asked for: state [B, nstep, nq+nv+na] (the state after each
+    step), qacc [B, nstep, nv] (each step's first mj_forward), fwdinv [B, nstep] (the driver's
+    solver_fwdinv[1]), and with status=True (status [B], steps_done [B]). An instance whose
+    forward reports constraint rows or a bad qpos / qvel / qacc stops: it is not advanced at
+    that step or later, its remaining state rows repeat the last good state, its remaining
+    qacc and fwdinv rows are 0, steps_done counts its completed steps and its status word
+    keeps the bits. The final state stays in the mirror (field("qpos"), ...), and so do the
+    last ctrl / qfrc_applied / xfrc_applied rows used."""
+    m = self.m
+    qpos = np.ascontiguousarray(qpos, dtype=np.float64).reshape(-1, self.nq)
+    B, T = qpos.shape[0], int(nstep)
+    qvel = np.ascontiguousarray(qvel, dtype=np.float64).reshape(B, self.nv)
+    rin, rout = RolloutIn(), RolloutOut()
+    rin.size, rout.size = ctypes.sizeof(RolloutIn), ctypes.sizeof(RolloutOut)
+    rin.qpos, rin.qvel = qpos.ctypes.data, qvel.ctypes.data
+    keep = [qpos, qvel]
+    if act is not None and m.na:
+      act = np.ascontiguousarray(act, dtype=np.float64).reshape(B, m.na)
+      rin.act = act.ctypes.data
+      keep.append(act)
+    for name, arr, n in (("ctrl", ctrl, m.nu), ("qfrc_applied", qfrc_applied, self.nv),
+                         ("xfrc_applied", xfrc_applied, 6 * m.nbody)):
+      if arr is None or not n:
+        continue
+      arr = np.ascontiguousarray(arr, dtype=np.float64)
+      if arr.size == B * n:
+        mode = ROLLOUT_HELD
+      elif arr.size == B * T * n:
+        mode = ROLLOUT_PERSTEP
+      else:
+        raise MJHIPError(f"rollout: {name} holds {arr.size} values, expected {B}x{n} or "
+                         f"{B}x{T}x{n}")
+      setattr(rin, name, arr.ctypes.data)
+      setattr(rin, name + "_mode", mode)
+      keep.append(arr)
+    res = []
+    if state:
+      s = np.zeros((B, T, self.nq + self.nv + m.na))
+      rout.state = s.ctypes.data
+      res.append(s)
+    if qacc:
+      a = np.zeros((B, T, self.nv))
+      rout.qacc = a.ctypes.data
+      res.append(a)
+    if fwdinv:
+      f = np.zeros((B, T))
+      rout.fwdinv = f.ctypes.data
+      res.append(f)
+    st = np.zeros(B, dtype=np.int32)
+    done = np.zeros(B, dtype=np.int32)
+    flags = STEP_FWDINV if fwdinv else 0
+    rc = lib().mjhip_rolloutBatch(self.ctx, B, T, ctypes.byref(rin), ctypes.byref(rout), flags,
+                                  st.ctypes.data, done.ctypes.data)
+    _check(rc, "mjhip_rolloutBatch")        # per-instance flags come back in `st`
+    if status:
+      res += [st, done]
+    return res[0] if len(res) == 1 else tuple(res)
+
+  def step(self, qpos, qvel, **kw):
+    """One mj_step per instance: rollout(nstep=1) with the step axis dropped from state,
+    qacc and fwdinv."""
+    res = self.rollout(qpos, qvel, 1, **kw)
+    drop = lambda a: a[:, 0] if a.ndim >= 2 and a.dtype == np.float64 else a
+    return drop(res) if isinstance(res, np.ndarray) else tuple(drop(a) for a in res)
 
   def actuation(self, B=None, ctrl=None, act=None, status=False):
     """Batched mj_fwdActuation over the actuator_length, actuator_velocity and
