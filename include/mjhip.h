@@ -360,6 +360,16 @@ MJHIP_API int mjhip_contextLastPath(const mjhipContext* c);
  * the library cannot see it (call mjhip_mirrorUpload on any field to have them rewritten). */
 MJHIP_API int mjhip_contextConstStores(const mjhipContext* c);
 MJHIP_API int mjhip_contextConstLaunches(const mjhipContext* c);
+/* The qM hand-off. The fused straight-line kernel k_all_<name> hands some rows of qM from its
+ * position stage to its factorization stage in LDS that is idle at that point, instead of
+ * re-reading them from the mirror; qM itself is stored as ever, and every result is bit for
+ * bit the same. By default a bundled kernel does so from batch 49,152 on, where L2 no longer
+ * serves the re-read; MJHIP_QM_HANDOFF in the environment at mjhip_contextCreate changes
+ * that: 1 at every batch, 0 never (a run-time code object has the one kernel it was generated
+ * with, which hands at every batch). Returns the doubles per instance handed by the k_all
+ * kernel this context launches at such batches: 0 with the generic kernel, for a model where
+ * no row fits, and with MJHIP_QM_HANDOFF=0. */
+MJHIP_API int mjhip_contextQmHandoff(const mjhipContext* c);
 /* the constraint kernel the context's last straight-line call launched, e.g.
  * "k_constraint_coop<16, false, true, false>" (the work-list kernel of a limits-only model) or
  * "k_constraint<true, true, false>"; "none" when it launched none (profiles name it) */

@@ -67,12 +67,25 @@ FUSE = True       # one launch running the three stage bodies back to back per w
 VA_RECOMPUTE = False
 # lanes per workgroup of each stage kernel: 64 = one instance block per wave; 32 = a block
 # split over two half-filled waves (twice the waves per SIMD, same mirror layout)
-# Experiment (round 2, off): k_all hands qM from the pos stage to the fac stage in a
-# kernel-local array the compiler promotes to registers, instead of fac re-reading it from
-# the mirror (the staged kernels pass nullptr and keep the re-read). Exact, but the 243 qM
-# values live across pos's post-order push k_all from 20 B to 1,968 B of scratch per lane
-# (tools/kernel_resources.py), and every spill reload waits for the store stream.
-QM_FORWARD = False
+# k_all hands the qM rows of qm_handoff_plan from the pos stage to the fac stage in LDS that
+# is dead at that point (qo_lds, the tail of the trig/stack region, and each hinge's sin/cos
+# pair once its body's pass-2 pre-visit has read it) instead of fac re-reading them from the
+# mirror: the HO = true instantiation of the pos and fac bodies, which only k_all and the
+# host entry select. A handed entry is never re-read, so its mirror store streams there.
+# (Round 2 handed all of qM in registers instead: exact, but the 243 values live across
+# pos's post-order pushed k_all from 20 B to 1,968 B of scratch per lane.)
+# QM_ORDER: "early" hands the first-produced rows (the longest store-to-load distance),
+# "late" the last-produced ones, both under the same liveness rule. Both fill the pool (75
+# doubles for the humanoid); late measured 0.4% faster on the bench step in an alternated A/B
+# (DESIGN.md §Measurements, round 9).
+QM_HANDOFF = True
+QM_ORDER = "late"
+# batches from which the launch functions pick the HO instantiation by default: the same
+# threshold as SV, for the same reason. Below it L2 is not oversubscribed, the fac stage's
+# re-read of qM is served there, and the hand-off only adds LDS traffic to a latency-bound
+# wave (batch 4,096 with contacts: 0.3% slower with it in a 12-run A/B; 65,536: 1.3% faster).
+# Mirror::qm_handoff = 2 (MJHIP_QM_HANDOFF=1) hands at every batch, 0 at none.
+QM_HANDOFF_MIN_B = 49152      # = NT_SV_MIN_B (below)
 # The va stage's tree pass keeps the cdof of the dofs on the current root-to-body path in an
 # LDS stack (written at a body's pre-visit, read back for the projections at its post-visit)
 # instead of re-reading them from the mirror. The stack shares k_all's trig region, which is
@@ -387,10 +400,76 @@ def k_all_lds_bytes(m, va_slots=None) -> int:
   return 8 * sum(_lds_doubles(m, M.va_nslot))
 
 
+def qm_row(M, k) -> list:
+  """The qM entries of dof k's row (mj_crb: the dof, then its ancestors), in stored order."""
+  n, j = 0, k
+  while j >= 0:
+    n += 1
+    j = M.dparent[j]
+  return list(range(M.Madr[k], M.Madr[k] + n))
+
+
+def qm_handoff_plan(m, va_slots=None, order=None) -> dict:
+  """{qM index -> LDS slot} of the entries k_all's pos stage hands to its fac stage on-chip.
+
+  A slot is one double per lane at [slot*64 + lane] of the trig/stack region (slots below
+  its rows, _lds_doubles(m, slots, 64)[0] / 64) or of qo_lds (the slots from there on). Three
+  pools, none of which adds a byte to k_all's static LDS:
+    qo_lds              written by the va stage only, so free during all of pos and fac;
+    the region's tail   the rows past the hinges' sin/cos pairs, the va stage's as well;
+    a hinge's pair      free once its body's pass-2 pre-visit has read it (_emit_frame), and
+                        qM rows are produced at post-visits only.
+  A handed value stays in its slot until the fac stage, so slots are never reused. A row is
+  handed whole or not at all, and a row of constants (dof_simplenum) never. order "early":
+  rows in production order, each taken when enough slots are free at its post-visit; "late":
+  from the last-produced row backwards, each preferring the slots released last. Empty when
+  the switch is off or less than one row fits."""
+  order = QM_ORDER if order is None else order
+  assert order in ("early", "late"), order
+  M = m if isinstance(m, _Model) else _Model(m, va_slots, handoff=False)
+  m = M.m
+  if not QM_HANDOFF or not FUSE or ALL_LANES > 64:
+    return {}
+  nreg, nqo = _lds_doubles(m, M.va_nslot, 64)
+  rows = nreg // 64                     # of the trig/stack region (max(1, ...) // 64 = 0: none)
+  events = []
+  M.dfs(lambda b: events.append(("pre", b)), lambda b: events.append(("post", b)))
+  when = {ev: t for t, ev in enumerate(events)}
+  # slot -> the event after which it is free (-1: from the start of the pos stage)
+  free_from = {s: -1 for s in range(2 * len(M.trig), rows)}
+  if m.nv > 0:
+    free_from.update({rows + k: -1 for k in range(nqo // 64)})
+  if not (VA_RECOMPUTE and FUSE):       # that experiment reads trig throughout the va stage
+    for j, h in M.trig.items():
+      t = when[("pre", int(m.jnt_bodyid[j]))]
+      free_from[2 * h] = free_from[2 * h + 1] = t
+  produced = [(when[("post", M.dbody[k])], k) for k in range(M.nv) if not M.simplenum[k]]
+  produced.sort(reverse=order == "late")
+  plan, taken = {}, set()
+  for t, k in produced:
+    entries = qm_row(M, k)
+    free = sorted((s for s in free_from if free_from[s] < t and s not in taken),
+                  key=lambda s: (free_from[s], s), reverse=order == "late")
+    if len(free) < len(entries):
+      continue
+    for a, s in zip(entries, free):
+      plan[a] = s
+      taken.add(s)
+  return plan
+
+
+def _ho_ref(M, slot, st) -> str:
+  """The arguments (array, row, stride, lane) of handQM / takeQM for a plan slot in stage st:
+  each LDS array is reached through its own __restrict__ pointer only."""
+  rows = _lds_doubles(M.m, M.va_nslot, 64)[0] // 64
+  li, ls = _ll(st)
+  return f"trig, {slot}, {ls}, {li}" if slot < rows else f"qo_lds, {slot - rows}, {ls}, {li}"
+
+
 class _Model:
   """Model constants the emitters share."""
 
-  def __init__(self, m, va_slots=None):
+  def __init__(self, m, va_slots=None, handoff=None):
     self.m = m
     self.nbody, self.nv, self.nq, self.njnt = m.nbody, m.nv, m.nq, m.njnt
     self.parent = [int(x) for x in m.body_parentid]
@@ -433,6 +512,8 @@ class _Model:
     self.va_slot, depth = va_slot_plan(m, va_slots)
     self.va_nslot = min(va_slots, depth)
     self.spatial = set(spatial_tendons(m))
+    # QM_HANDOFF: {qM index: LDS slot} of the entries the HO instantiation hands on-chip
+    self.handoff = qm_handoff_plan(self) if handoff is None or handoff else {}
     # CONST_ONCE: {(field, index): expression} in emission order, and the declarations the
     # expressions name
     self.consts, self.const_decls = {}, []
@@ -502,11 +583,13 @@ class _Stage:
 
   def st(self, field, k, expr):
     self.stored.add(field)
-    if field == "qM" and QM_FORWARD:
-      self.E(f"{{ const double v_ = {expr}; if (qmr) qmr[{k}] = v_;")
+    if field == "qM" and k in self.M.handoff:
+      # a handed entry: the mirror store (qM is an output; generate() makes it a streaming
+      # store in the HO instantiation) and the LDS slot the fac stage takes it from
+      self.E(f"{{ const double v_ = {expr};")
       if self.store_fields is None or field in self.store_fields:
-        self.E(f"  P_qM[{k}*64] = v_;")
-      self.E("}")
+        self.E(f"P_qM[{k}*64] = v_;")
+      self.E(f"mjh::handQM<HO>({_ho_ref(self.M, self.M.handoff[k], 'pos')}, v_); }}")
       return
     if self.store_fields is None or field in self.store_fields:
       self.E(f"P_{field}[{k}*64] = {expr};")
@@ -1040,11 +1123,7 @@ def _gen_pos(M: _Model, store_fields=None) -> str:
     # qM rows of this body's dofs (mj_crb :1370-1399); qM starts zeroed (mju_zero)
     for k in range(M.bdofadr[i], M.bdofadr[i] + M.bdofnum[i]):
       adr = M.Madr[k]
-      rowlen = 0
-      j = k
-      while j >= 0:
-        rowlen += 1
-        j = M.dparent[j]
+      rowlen = len(qm_row(M, k))
       if M.simplenum[k]:
         G.st("qM", adr, lit(m.dof_M0[k]))
         for a in range(adr + 1, adr + rowlen):
@@ -1138,13 +1217,13 @@ def _gen_fac(M: _Model, store_fields=None) -> str:
   nv = M.nv
   G.prologue()
   G.pointers(["qM", "qLD", "qLDiagInv"])
-  for a in range(m.nM):
-    E(f"const double M_{a} = qmr ? qmr[{a}] : P_qM[{a}*64];" if QM_FORWARD
-      else f"const double M_{a} = P_qM[{a}*64];")
   rownnz = [int(x) for x in m.C_rownnz]
   rowadr = [int(x) for x in m.C_rowadr]
   colind = [int(x) for x in m.C_colind]
   mapM2C = [int(x) for x in m.mapM2C]
+  for a in range(m.nM):
+    E(f"const double M_{a} = mjh::takeQM<HO>({_ho_ref(M, M.handoff[a], 'fac')}, P_qM + {a}*64);"
+      if a in M.handoff else f"const double M_{a} = P_qM[{a}*64];")
   E(f"double {', '.join(f'L_{c} = M_{mapM2C[c]}' for c in range(m.nC))};")
   for k in range(nv - 1, -1, -1):
     ra = rowadr[k]
@@ -1694,21 +1773,26 @@ _SIG = {
     "pos": ("const double* __restrict__ qpos_in, const double* __restrict__ qvel_in, "
             "const double* __restrict__ qacc_in, int* __restrict__ worklist, "
             "int* __restrict__ worklist_count, int* __restrict__ worklist_next, "
-            "int* __restrict__ efc_count, double* __restrict__ trig, double* __restrict__ qmr",
+            "int* __restrict__ efc_count, double* __restrict__ trig, "
+            "double* __restrict__ qo_lds",
             "qpos_in, qvel_in, qacc_in, worklist, worklist_count, worklist_next, efc_count, trig, "
-            "qmr"),
-    "fac": ("int* __restrict__ efc_count, const double* __restrict__ qmr", "efc_count, qmr"),
+            "qo_lds"),
+    "fac": ("int* __restrict__ efc_count, const double* __restrict__ trig, "
+            "const double* __restrict__ qo_lds", "efc_count, trig, qo_lds"),
     "va": ("double* __restrict__ qfrc_out, int* __restrict__ status, "
            "int* __restrict__ efc_count, double* __restrict__ qo_lds, "
            "double* __restrict__ trig",
            "qfrc_out, status, efc_count, qo_lds, trig"),
 }
+# the pos and fac bodies take the qM hand-off's switch (QM_HANDOFF); only k_all and the host
+# entry instantiate it set, and the LDS pointers of every other caller may be null
+_HO_PARAM = {"pos": ", bool HO = false", "fac": ", bool HO = false", "va": ""}
 _GEN = {"pos": lambda M, sf: _gen_pos(M, sf), "fac": lambda M, sf: _gen_fac(M, sf),
         "va": lambda M, sf: _gen_va(M, sf)}
 
 
 def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bool = False,
-             va_slots=None) -> str:
+             va_slots=None, handoff=None) -> str:
   """HIP source of the four stage kernels of model `m` (skipstage = mjSTAGE_NONE).
 
   Also emits `fast_body_<name>`, which runs fast_const_<name> and then the stage bodies for
@@ -1723,22 +1807,30 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
   extern_c: give k_all_<name> C linkage (a run-time code object, specialize.py, whose
   kernel mjhip_contextLoadKernel looks up by name).
   va_slots: capacity of the va stage's cdof stack (default VA_LDS_SLOTS).
+  handoff: False leaves the qM hand-off out of the text (default QM_HANDOFF).
   """
   why = fast_path_supported(m)
   if why:
     raise ValueError(f"model '{name}' cannot use the straight-line kernels: {why}")
-  M = _Model(m, va_slots)
+  M = _Model(m, va_slots, handoff)
+  # the pos and fac bodies' HO argument where the hand-off is on (k_all's kernel template
+  # argument, the literal in the host entry and in a run-time code object)
+  ho = {st: "" if not _HO_PARAM[st] else ", true" if M.handoff else ", false" for st in STAGES}
   # the region the pos stage's trig and the va stage's cdof stack share, and qo_lds, in
   # doubles per 64 lanes; every wrapper that runs the va body declares the region
   nreg64 = _lds_doubles(m, M.va_nslot, 64)[0]
   assert 8 * sum(_lds_doubles(m, M.va_nslot)) <= LDS_BUDGET, \
       f"k_all_{name}: {8 * sum(_lds_doubles(m, M.va_nslot))} B of LDS, three workgroups per CU"
+  # the hand-off lives in the arrays declared below and nowhere else: k_all's static LDS is
+  # what it is without it
+  assert all(0 <= s < sum(_lds_doubles(m, M.va_nslot, 64)) // 64 for s in M.handoff.values())
+  assert len(set(M.handoff.values())) == len(M.handoff)
   bodies = {st: _GEN[st](M, store_fields) for st in STAGES}
   if NT_STORES:
     import re
     # the fac stage's re-reads stay temporal; the other stages' re-reads stream only in the
     # SV = true instantiation of k_all (a batch large enough to oversubscribe L2, NT_SV_MIN_B)
-    reread = set(re.findall(r"= P_(\w+)\[", bodies["fac"]))
+    reread = set(re.findall(r"= P_(\w+)\[", bodies["fac"])) | ({"qM"} if M.handoff else set())
     later = set(re.findall(r"= P_(\w+)\[", "\n".join(bodies.values()))) - reread
     if NT_TEMPORAL is not None:
       reread, later = set(NT_TEMPORAL), set()
@@ -1746,6 +1838,10 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
 
     def nt(line):
       mt = store.match(line)
+      if mt and mt.group(2) == "qM" and int(mt.group(3)) in M.handoff and "qM" in reread:
+        # a handed entry is not re-read where it is handed: it streams there like every
+        # write-only field, and stays temporal for the kernels whose fac stage re-reads it
+        return f"{mt.group(1)}MJH_NT_STORE_IF(HO, P_qM[{mt.group(3)}*64], {mt.group(4)});"
       if not mt or mt.group(2) in reread:
         return line
       if mt.group(2) in later:
@@ -1788,7 +1884,7 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
     out.append("#if defined(__clang__)\n#pragma clang fp contract(off)\n#endif")
   for st in STAGES:
     params, args = _SIG[st]
-    out.append(f"template <bool SV = true, bool FD = false>\n"
+    out.append(f"template <bool SV = true, bool FD = false{_HO_PARAM[st]}>\n"
                f"MJH_HD void fast_{st}_{name}(const Mirror& mr, int blk, int lane, int B, "
                f"{params}) {{\n{bodies[st]}\n}}\n")
   const_call = ""
@@ -1805,11 +1901,10 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
     int* __restrict__ worklist_count, int* __restrict__ worklist_next,
     int* __restrict__ efc_count) {{
   double trig[{nreg64}];   // LDS on the device (k_pos's trig, then k_va's cdof stack)
-  double qo_lds[{64 * max(M.nv, 1)}];             // LDS on the device (k_va)
-  double qmr[{max(1, m.nM)}];                        // registers on the device (k_all)
+  double qo_lds[{64 * max(M.nv, 1)}];             // LDS on the device (k_va; the qM hand-off)
   const bool fd = mr.fd_elide && blk >= mr.full_blk;   // mjd_inverseFD's perturbed blocks
-""" + const_call + "".join(f"  if (fd) fast_{st}_{name}<true, true>(mr, blk, lane, B, {_SIG[st][1]});\n"
-              f"  else fast_{st}_{name}<true, false>(mr, blk, lane, B, {_SIG[st][1]});\n"
+""" + const_call + "".join(f"  if (fd) fast_{st}_{name}<true, true{ho[st]}>(mr, blk, lane, B, {_SIG[st][1]});\n"
+              f"  else fast_{st}_{name}<true, false{ho[st]}>(mr, blk, lane, B, {_SIG[st][1]});\n"
               for st in STAGES)
              + (f"""  if (qfrc_out && (long)blk*64 + lane < B) {{
     for (int k = 0; k < {M.nv}; k++) qfrc_out[((long)blk*64 + lane)*{M.nv} + k] = qo_lds[lane*{M.nv} + k];
@@ -1821,11 +1916,10 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
     tail = ""
     nl = LANES[st]
     sub = 64 // nl    # workgroups per 64-instance block
-    params = params.replace(", double* __restrict__ qmr", "").replace(
-        ", const double* __restrict__ qmr", "")
-    args = args.replace(", qmr", ", nullptr")      # staged: qM goes through the mirror
-    if st == "pos":
+    if st == "pos":                                # staged: qM goes through the mirror
       params = params.replace(", double* __restrict__ trig", "")
+      params = params.replace(", double* __restrict__ qo_lds", "")
+      args = args.replace(", qo_lds", ", nullptr")
       decl = f"  __shared__ double trig[{max(1, 2 * len(M.trig) * nl)}];\n"
     elif st == "va":
       params = params.replace(", double* __restrict__ qo_lds", "")
@@ -1843,6 +1937,9 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
                 f"  double* dst = qfrc_out + r0*{M.nv};\n"
                 f"  for (long r = threadIdx.x; r < n; r += {nl}) dst[r] = qo_lds[r];\n")
     else:
+      params = params.replace(", const double* __restrict__ trig", "")
+      params = params.replace(", const double* __restrict__ qo_lds", "")
+      args = args.replace(", trig, qo_lds", ", nullptr, nullptr")
       decl = ""
     if sub == 1:
       bl = "blockIdx.x, threadIdx.x"
@@ -1881,12 +1978,15 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
   # The next call's work-list counter is zeroed by the launch's first thread, before any
   # instance bound, so an empty range still hands the counters on.
   # SV: the va stage's re-read fields stream too (a batch that oversubscribes L2); a
-  # run-time code object (C linkage, no template) has the SV = true kernel only
-  tmpl = "" if extern_c else "template <bool SV, bool FD>\n"
+  # run-time code object (C linkage, no template) has the SV = true kernel only.
+  # HO: the pos stage hands the qM entries of M.handoff to the fac stage in LDS
+  # (QM_HANDOFF); a run-time code object's one kernel has it set whenever the plan is not empty
+  tmpl = "" if extern_c else "template <bool SV, bool FD, bool HO>\n"
   sv = "true" if extern_c else "SV"
+  kho = ho if extern_c else {st: ", HO" if _HO_PARAM[st] else "" for st in STAGES}
 
   def stage_calls(fd, ind="  "):
-    return "\n".join(f"{ind}fast_{st}_{name}<{sv}, {fd}>(mr, {bl}, B, "
+    return "\n".join(f"{ind}fast_{st}_{name}<{sv}, {fd}{kho[st]}>(mr, {bl}, B, "
                      f"{_SIG[st][1].replace('worklist_next', 'nullptr')});\n"
                      f"{ind}asm volatile(\"\" ::: \"memory\"); MJH_SCHED_FENCE(); MJH_PHASE({20 + k});"
                      for k, st in enumerate(STAGES))
@@ -1903,7 +2003,6 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
     int* __restrict__ efc_count, const int* __restrict__ range) {{
   __shared__ double trig[{ntrig}];
   __shared__ double qo_lds[{nqo}];
-  double qmr[{max(1, m.nM)}];
   if (worklist_next && blockIdx.x == 0 && threadIdx.x == 0) *worklist_next = 0;
   int blk0 = 0;
   if (range) {{ blk0 = range[0] >> 6; B = range[1]; }}
@@ -1915,7 +2014,7 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
   # -- runs on a second stream beside k_sfv, and the assembly kernel (mjhip.hip k_assemble)
   # joins them (mjhip.hip launch_inverse). Same stage bodies as k_all, so the same results.
   if M.cmode == "all" and not extern_c:
-    pos_args = _SIG["pos"][1].replace("trig, qmr", "trig, nullptr")
+    pos_args = _SIG["pos"][1].replace("trig, qo_lds", "trig, nullptr")
     out.append(f"""template <bool SV>
 __global__ __launch_bounds__(64, 1) void k_spos_{name}(Mirror mr, int B,
     const double* __restrict__ qpos_in, const double* __restrict__ qvel_in,
@@ -1931,7 +2030,7 @@ __global__ __launch_bounds__(64, 1) void k_sfv_{name}(Mirror mr, int B,
     double* __restrict__ qfrc_out, int* __restrict__ status, int* __restrict__ efc_count) {{
   __shared__ double qo_lds[{nqo}];
 {stk_decl}  MJH_PHASE(20);     // the position span runs from k_spos's start to here (launch gap included)
-  fast_fac_{name}<SV>(mr, blockIdx.x, threadIdx.x, B, efc_count, nullptr);
+  fast_fac_{name}<SV>(mr, blockIdx.x, threadIdx.x, B, efc_count, nullptr, nullptr);
   asm volatile("" ::: "memory"); MJH_SCHED_FENCE(); MJH_PHASE(21);
   fast_va_{name}<SV>(mr, blockIdx.x, threadIdx.x, B, qfrc_out, status, efc_count, qo_lds,
                      {stk_arg});
@@ -2089,7 +2188,6 @@ __global__ __launch_bounds__(64, 1) void k_fdall_{name}(Mirror mr, int B, int ni
   if (worklist_next && blockIdx.x == 0 && threadIdx.x == 0) *worklist_next = 0;
   const int nblk = B / 64;                  // B: a whole number of waves
   if ((int)blockIdx.x < nblk) {{
-    double qmr[{max(1, m.nM)}];
     const double* qpos_in = nullptr;
     const double* qvel_in = nullptr;
     const double* qacc_in = nullptr;
@@ -2214,6 +2312,14 @@ __global__ __launch_bounds__(64, 1) void k_acc_{name}(Mirror mr, int B,
 }}
 {"" if shared else "static "}int const_stores_{name}() {{ return {nconst}; }}""")
   assert len(M.consts) == nconst, "a constant store emitted after fast_const was written"
+  # the qM entries per instance that k_all's HO instantiation hands on-chip
+  # (mjhip_contextQmHandoff); a run-time code object carries the count as a device global
+  if extern_c:
+    out.append(f'extern "C" __device__ __attribute__((used)) int k_qm_handoff_{name} = '
+               f"{len(M.handoff)};")
+  else:
+    out.append(f"{'' if shared else 'static '}int qm_handoff_{name}() "
+               f"{{ return {len(M.handoff) if FUSE else 0}; }}")
   out.append(f"""{"" if shared else "static "}void launch_fast_{name}(dim3 g, dim3 b, hipStream_t s, const Mirror& mr,
     int B, const double* qpos_in, const double* qvel_in, const double* qacc_in, double* qfrc_out,
     int* status, int* worklist, int* worklist_count, int* worklist_next, int* efc_count,
@@ -2225,6 +2331,14 @@ __global__ __launch_bounds__(64, 1) void k_acc_{name}(Mirror mr, int B,
     if not extern_c and M.cmode in ("none", "list"):   # mjd_inverseFD's perturbed instances
       variants = ((f"mr.fd_elide && B >= {NT_SV_MIN_B}", "<true, true>"),
                   ("mr.fd_elide", "<false, true>")) + variants
+    if not extern_c:   # each with the qM hand-off (Mirror::qm_handoff) where there is a plan
+      out.append(f"  const bool ho = mr.qm_handoff > 1 || (mr.qm_handoff == 1 && "
+                 f"B >= {QM_HANDOFF_MIN_B});")
+      variants = tuple(x for cond, v in variants for x in
+                       ([(f"ho && ({cond})", v[:-1] + ", true>")] if M.handoff else []) +
+                       [(cond, v[:-1] + ", false>")])
+      if not M.handoff:
+        out.append("  (void)ho;")
     for cond, v in variants:
       out.append(f"  if ({cond}) {{\n    hipLaunchKernelGGL((k_all_{name}{v}), {gb}, 0, s, mr, B, "
                  f"qpos_in, qvel_in, qacc_in, qfrc_out, status, worklist, worklist_count, "
@@ -2232,7 +2346,8 @@ __global__ __launch_bounds__(64, 1) void k_acc_{name}(Mirror mr, int B,
   else:   # staged kernels (experiments): the whole [0, B) range only
     out.append("  if (range) return;   // device-side ranges need k_all")
     for st in STAGES:
-      args = _SIG[st][1].replace(", trig", "").replace(", qo_lds", "").replace(", qmr", ", nullptr")
+      args = _SIG["va"][1].replace(", trig", "").replace(", qo_lds", "") if st == "va" else \
+          _SIG[st][1].replace(", trig, qo_lds", "")
       gb = "g, b" if LANES[st] == 64 else f"dim3(g.x*{64 // LANES[st]}), dim3({LANES[st]})"
       out.append(f"  hipLaunchKernelGGL(k_{st}_{name}, {gb}, 0, s, mr, B, {args});")
   out.append("}")
@@ -2335,6 +2450,7 @@ def generate_registries(entries) -> tuple:
       if CONST_ONCE:
         main.append(f"void launch_const_{name}(hipStream_t, const Mirror&, int);")
         main.append(f"int const_stores_{name}();")
+      main.append(f"int qm_handoff_{name}();")
       if constraint_mode(m) == "all":
         main.append(f"void launch_split_{name}(hipStream_t, const Mirror&, int, int, "
                     "const double*, const double*, const double*, int*, int*, int*);")
@@ -2349,11 +2465,11 @@ def generate_registries(entries) -> tuple:
     const = f"launch_const_{name}, const_stores_{name}" if CONST_ONCE else "nullptr, nullptr"
     reg.append(f'  {{0x{fields.model_signature(m):016x}ull, launch_fast_{name}, "{name}", '
                f'{CONSTRAINT_MODES[constraint_mode(m)]}, {fns}, launch_skip_{name}, {split}, '
-               f'{fdall}, lds_fast_{name}, {const}}},')
+               f'{fdall}, lds_fast_{name}, {const}, qm_handoff_{name}}},')
   main.append("static const FastKernelEntry g_fast_kernels[] = {")
   main.extend(reg)
   main.append("  {0ull, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, "
-              "nullptr, nullptr}};")
+              "nullptr, nullptr, nullptr}};")
   return "\n".join(main) + "\n", "\n".join(exact) + "\n"
 
 
@@ -2371,9 +2487,9 @@ def generate_registry(entries) -> str:
     const = f"launch_const_{name}, const_stores_{name}" if CONST_ONCE else "nullptr, nullptr"
     reg.append(f'  {{0x{fields.model_signature(m):016x}ull, launch_fast_{name}, "{name}", '
                f'{CONSTRAINT_MODES[constraint_mode(m)]}, {fns}, launch_skip_{name}, {split}, '
-               f'{fdall}, lds_fast_{name}, {const}}},')
+               f'{fdall}, lds_fast_{name}, {const}, qm_handoff_{name}}},')
   out.append("static const FastKernelEntry g_fast_kernels[] = {")
   out.extend(reg)
   out.append("  {0ull, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, "
-             "nullptr, nullptr}};")
+             "nullptr, nullptr, nullptr}};")
   return "\n".join(out) + "\n"

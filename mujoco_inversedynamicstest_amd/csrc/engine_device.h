@@ -533,6 +533,19 @@ template <class A> MJH_HD void put6(double* stk, int s, int stride, int lane, A 
 template <class R> MJH_HD void get6(R r, const double* stk, int s, int stride, int lane) {
   for (int c = 0; c < 6; c++) r[c] = stk[(s*6 + c)*stride + lane];
 }
+// The straight-line k_all's qM hand-off (codegen.py qm_handoff_plan): the pos stage leaves a
+// handed qM entry in an LDS slot that is dead at that point (one double per lane, at
+// lds[slot*stride + lane]) and the fac stage takes it from there instead of re-reading the
+// mirror. HO is the kernel's template argument: without it the slot is never touched and the
+// entry comes from the mirror, as in every kernel but k_all.
+template <bool HO> MJH_HD void handQM(double* lds, int slot, int stride, int lane, double v) {
+  if constexpr (HO) lds[slot*stride + lane] = v;
+}
+template <bool HO>
+MJH_HD double takeQM(const double* lds, int slot, int stride, int lane, const double* mirror) {
+  if constexpr (HO) return lds[slot*stride + lane];
+  else return *mirror;
+}
 template <class R, class A> MJH_HD void scl(R r, A a, double s, int n) {
   for (int i = 0; i < n; i++) r[i] = a[i]*s;
 }
@@ -9744,6 +9757,10 @@ struct Mirror {
   // kernel reads
   int fd_elide;
   int full_blk;
+  // when the generated launch functions pick k_all's HO instantiation (the qM hand-off
+  // through LDS, codegen.py qm_handoff_plan): 0 never, 1 from batch codegen.QM_HANDOFF_MIN_B
+  // on, 2 at every batch; set at context creation (MJHIP_QM_HANDOFF)
+  int qm_handoff;
 #define XD(name, d0, d1, stage) int name##_n;
   MJHIP_DATA_ACTIVATION
 #undef XD

@@ -52,6 +52,10 @@ struct FastKernelEntry {
   // its code object (mjhip_contextLoadKernel)
   void (*launch_const)(hipStream_t, const Mirror&, int);
   int (*const_stores)();
+  // qM entries per instance that k_all's HO instantiation hands from its pos stage to its fac
+  // stage in LDS (codegen.py qm_handoff_plan), launched when Mirror::qm_handoff is set; 0
+  // where nothing fits. Null for run-time kernels: the count is a global of the code object
+  int (*qm_handoff)();
 };
 
 // static LDS a k_all workgroup may hold while four of them share a CU's 160 KB

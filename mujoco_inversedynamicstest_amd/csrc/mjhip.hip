@@ -571,6 +571,7 @@ struct mjhipContext_ {
   hipDeviceptr_t rt_tbuf = nullptr;        // the code object's mjh_tbuf (null: none)
   hipFunction_t rt_const_fn = nullptr;     // the code object's k_const_<name>
   int rt_nconst = 0;                       // and its k_const_count_<name>
+  int rt_nhand = 0;                        // and its k_qm_handoff_<name> (0: none)
   // the model-constant output slots the generated stage bodies leave to k_const may not hold
   // their values: set at creation, by mjhip_contextLoadKernel (another code object carries its
   // own constants) and by every mjhip_mirrorUpload; cleared by ensure_const
@@ -953,6 +954,12 @@ MJHIP_API int mjhip_contextCreateCapped(const mjhipModel* caller, int device, in
       if (e->sig == c->sig) c->fast = e;
     }
   }
+  // the qM hand-off of the bundled k_all kernels (codegen.py QM_HANDOFF). Default: their HO
+  // instantiation from the batch at which L2 no longer serves the re-read
+  // (codegen.QM_HANDOFF_MIN_B); MJHIP_QM_HANDOFF=1: at every batch; =0: never (the fac stage
+  // re-reads all of qM)
+  const char* ho = getenv("MJHIP_QM_HANDOFF");
+  c->mirror.qm_handoff = !ho ? 1 : ho[0] == '0' ? 0 : ho[0] == '1' ? 2 : 1;
   if (c->fast && c->fast->lds_bytes) {
     // four k_all workgroups share a CU's LDS (one wave per SIMD): a kernel compiled over the
     // budget would run on three SIMDs of each CU
@@ -1158,6 +1165,17 @@ MJHIP_API int mjhip_contextLoadKernel(mjhipContext* c, const void* image, size_t
   c->rt_const_fn = cfn;
   c->rt_nconst = nconst;
   c->const_stale = true;
+  // the entries its k_all hands on-chip (an object without the count hands none)
+  const std::string hname = std::string("k_qm_handoff_") + name;
+  hipDeviceptr_t nhp = nullptr;
+  size_t nhbytes = 0;
+  c->rt_nhand = 0;
+  if (hipModuleGetGlobal(&nhp, &nhbytes, mod, hname.c_str()) != hipSuccess ||
+      nhbytes != sizeof(int) ||
+      hipMemcpy(&c->rt_nhand, (const void*)nhp, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
+    c->rt_nhand = 0;
+    (void)hipGetLastError();
+  }
   size_t tbytes = 0;                       // its per-stage timer pointer (MJH_TBUF_EXTERN)
   if (hipModuleGetGlobal(&c->rt_tbuf, &tbytes, mod, "mjh_tbuf") != hipSuccess ||
       tbytes != sizeof(void*)) {
@@ -1270,6 +1288,12 @@ MJHIP_API int mjhip_contextConstStores(const mjhipContext* c) {
   if (!c || !c->fast) return 0;
   if (c->fast == &c->rt) return c->rt_nconst;
   return c->fast->const_stores ? c->fast->const_stores() : 0;
+}
+
+MJHIP_API int mjhip_contextQmHandoff(const mjhipContext* c) {
+  if (!c || !c->fast) return 0;
+  if (c->fast == &c->rt) return c->rt_nhand;
+  return (c->mirror.qm_handoff && c->fast->qm_handoff) ? c->fast->qm_handoff() : 0;
 }
 
 MJHIP_API int mjhip_contextConstLaunches(const mjhipContext* c) {

@@ -61,6 +61,7 @@ SIGNATURES = {
     "mjhip_contextLastPath": (ctypes.c_int, [_V]),
     "mjhip_contextConstStores": (ctypes.c_int, [_V]),
     "mjhip_contextConstLaunches": (ctypes.c_int, [_V]),
+    "mjhip_contextQmHandoff": (ctypes.c_int, [_V]),
     "mjhip_contextConstraintKernel": (ctypes.c_char_p, [_V]),
     "mjhip_contextStream": (_V, [_V]),
     "mjhip_contextSetStream": (ctypes.c_int, [_V, _V]),
@@ -307,6 +308,13 @@ class InverseEngine:
     """Model-constant output slots per instance that the straight-line kernel leaves to its
     once-per-context k_const (0: it stores everything itself, or the generic kernel runs)."""
     return lib().mjhip_contextConstStores(self.ctx)
+
+  @property
+  def qm_handoff(self):
+    """qM entries per instance that this context's k_all hands from its pos stage to its fac
+    stage in LDS instead of through the mirror, at batches of 49,152 and more (at every batch
+    when MJHIP_QM_HANDOFF=1 was set as the engine was created; 0: none, or it was set to 0)."""
+    return lib().mjhip_contextQmHandoff(self.ctx)
 
   @property
   def const_launches(self):

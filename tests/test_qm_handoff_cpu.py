@@ -1,0 +1,228 @@
+"""The qM hand-off of the fused straight-line kernel (codegen.QM_HANDOFF): the plan, the
+generated text and the host build.
+
+k_all's pos stage leaves some rows of qM in LDS that is dead at that point (qo_lds, the tail
+of the trig/stack region, a hinge's sin/cos pair after its body's pass-2 pre-visit) and the fac
+stage takes them from there instead of re-reading the mirror. The plan may only use slots that
+are dead, k_all's static LDS may not grow, and no output may change by a bit.
+"""
+import ctypes
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+from mujoco_inversedynamicstest_amd import codegen, fields, host, models
+from mujoco_inversedynamicstest_amd.sampler import sample_states
+from oracle.oracle import Oracle
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+if HERE not in sys.path:
+  sys.path.insert(0, HERE)
+import test_codegen_cpu as cg  # noqa: E402
+
+# the headline model, one with ball joints and hinges, one with free joints only (no hinge)
+MODELS = (("humanoid", True), ("inertia", True), ("connect", True))
+ORDERS = ("early", "late")
+
+
+@pytest.fixture(scope="module", params=MODELS, ids=[n for n, _ in MODELS])
+def model(request):
+  name, dc = request.param
+  m = models.load(name, disable_contact=dc)
+  assert codegen.fast_path_supported(m) is None
+  return name, m
+
+
+def _walk(m):
+  """The pass-2 traversal on its own: [(kind, body)] depth-first, children descending."""
+  kids = {b: [] for b in range(m.nbody)}
+  for b in range(1, m.nbody):
+    kids[int(m.body_parentid[b])].append(b)
+  events, stack = [], [("pre", 0)]
+  while stack:
+    kind, b = stack.pop()
+    events.append((kind, b))
+    if kind == "pre":
+      stack.append(("post", b))
+      stack.extend(("pre", c) for c in sorted(kids[b]))     # popped in descending order
+  return events
+
+
+def _rowlen(m, k):
+  n = 0
+  while k >= 0:
+    n, k = n + 1, int(m.dof_parentid[k])
+  return n
+
+
+def _pools(m):
+  """(rows of the trig/stack region, its hinge pairs {joint: pair index}, qo_lds rows)."""
+  M = codegen._Model(m)
+  nreg, nqo = codegen._lds_doubles(m, M.va_nslot, 64)
+  hinges = [j for j in range(m.njnt) if int(m.jnt_type[j]) == codegen.HINGE]
+  trig = {j: h for h, j in enumerate(hinges)} if 0 < len(hinges) <= codegen.MAX_LDS_HINGES else {}
+  return nreg // 64, trig, nqo // 64
+
+
+def _resimulate_early(m):
+  """Handed doubles with order 'early', by counting alone: a row is taken at its post-visit
+  when the slots free by then, less those already given away, hold it."""
+  rows, trig, nqo = _pools(m)
+  free = rows - 2 * len(trig) + nqo
+  handed = 0
+  for kind, b in _walk(m):
+    if kind == "pre":
+      free += 2 * sum(1 for j in trig if int(m.jnt_bodyid[j]) == b)
+      continue
+    for k in range(int(m.body_dofadr[b]), int(m.body_dofadr[b]) + int(m.body_dofnum[b])):
+      if b and not int(m.dof_simplenum[k]) and _rowlen(m, k) <= free - handed:
+        handed += _rowlen(m, k)
+  return handed
+
+
+@pytest.mark.parametrize("order", ORDERS)
+def test_plan_uses_dead_slots_only(model, order):
+  name, m = model
+  plan = codegen.qm_handoff_plan(m, None, order)
+  rows, trig, nqo = _pools(m)
+  when = {ev: t for t, ev in enumerate(_walk(m))}
+  pair_of = {h: j for j, h in trig.items()}
+  # no two live entries share a slot (a handed value lives until the fac stage), and every
+  # slot lies in the arrays k_all declares anyway
+  assert len(set(plan.values())) == len(plan)
+  assert all(0 <= s < rows + nqo for s in plan.values())
+  assert len(plan) <= rows + nqo                      # handed doubles within the pool
+  # rows are whole
+  M = codegen._Model(m)
+  by_row = {k: codegen.qm_row(M, k) for k in range(m.nv)}
+  assert sorted(a for r in by_row.values() for a in r) == list(range(m.nM))
+  for k, entries in by_row.items():
+    assert [a == int(m.dof_Madr[k]) + i for i, a in enumerate(entries)] == [True] * _rowlen(m, k)
+    got = [a in plan for a in entries]
+    assert all(got) or not any(got), (name, k)
+    if any(got):
+      produced = when[("post", int(m.dof_bodyid[k]))]
+      for a in entries:
+        s = plan[a]
+        if s < 2 * len(trig):       # a hinge's pair: its body's pre-visit has read it by then
+          assert when[("pre", int(m.jnt_bodyid[pair_of[s // 2]]))] < produced, (name, k, s)
+  # k_all's static LDS is what it is with the hand-off off
+  on = codegen.generate(m, name)
+  off = codegen.generate(m, name, handoff=False)
+  lds = re.compile(r"__shared__ double (trig|qo_lds)\[(\d+)\];")
+  k_all = lambda t: lds.findall(t[t.index(f"void k_all_{name}("):])[:2]     # noqa: E731
+  assert k_all(on) == k_all(off)
+  assert 8 * sum(int(n) for _, n in k_all(on)) == codegen.k_all_lds_bytes(m)
+  assert "handQM" not in off and "takeQM" not in off and ", true, true>" not in off
+
+
+def test_humanoid_plan_matches_resimulation():
+  m = models.load("humanoid", disable_contact=True)
+  plan = codegen.qm_handoff_plan(m, None, "early")
+  assert len(plan) == _resimulate_early(m) > 0
+  assert codegen.qm_handoff_plan(m, None, "late")
+  assert codegen.k_all_lds_bytes(m) == 38400
+  # the default order is one of the two
+  assert codegen.qm_handoff_plan(m) == codegen.qm_handoff_plan(m, None, codegen.QM_ORDER)
+
+
+def test_resimulation_agrees_on_every_model(model):
+  name, m = model
+  assert len(codegen.qm_handoff_plan(m, None, "early")) == _resimulate_early(m)
+
+
+def test_generated_text(model):
+  name, m = model
+  M = codegen._Model(m)
+  plan = M.handoff
+  text = codegen.generate(m, name)
+  body = lambda st: text[text.index(f"MJH_HD void fast_{st}_{name}("):].split("\n}\n")[0]  # noqa: E731
+  fac, pos = body("fac"), body("pos")
+  # the fac stage loads from the mirror what was not handed, and takes the rest from LDS
+  assert len(re.findall(r"P_qM\[", fac)) == m.nM - len(plan)
+  assert fac.count("mjh::takeQM<HO>(") == len(plan)
+  rows = _pools(m)[0]
+  for a, s in plan.items():
+    arr, row = ("trig", s) if s < rows else ("qo_lds", s - rows)
+    # the same slot on both sides, each array through its own pointer
+    assert f"mjh::takeQM<HO>({arr}, {row}, 64, lane, P_qM + {a}*64);" in fac
+    hand = f"mjh::handQM<HO>({arr}, {row}, 64, lane, v_);"
+    assert pos.count(hand) == 1
+    # a handed entry's qM store streams where it is handed, and nowhere else
+    assert len(re.findall(rf"MJH_NT_STORE_IF\(HO, P_qM\[{a}\*64\], v_\);", pos)) == 1
+    assert not re.search(rf"^\s*P_qM\[{a}\*64\] = ", pos, re.M)
+    if arr == "trig" and row < 2 * len(M.trig):   # written only after the pair's last read
+      assert pos.rindex(f"trig[{row}*64 + lane]") < pos.index(hand)
+  # every other entry's store stays temporal for the fac stage's re-read
+  for a in set(range(m.nM)) - set(plan):
+    assert re.search(rf"^\s*P_qM\[{a}\*64\] = ", pos, re.M), a
+  # only k_all (and the host entry) select the hand-off
+  assert text.count(f"fast_pos_{name}<SV, false, HO>") == 1
+  assert text.count(f"fast_fac_{name}<SV, false, HO>") == 1
+  for kern in ("k_pos", "k_fac", "k_spos", "k_sfv", "k_fdall", "k_vaskip", "k_fdskip"):
+    at = text.find(f"void {kern}_{name}(")
+    if at >= 0:
+      assert not re.search(r"\bHO\b", text[at:].split("\n}\n")[0]), kern
+
+
+def test_launch_picks_handoff_by_switch_and_batch():
+  """Mirror::qm_handoff: 0 never, 1 from QM_HANDOFF_MIN_B on (the SV threshold), 2 always; every
+  SV/FD instantiation of k_all exists with and without the hand-off."""
+  m = models.load("humanoid", disable_contact=True)
+  text = codegen.generate(m, "humanoid")
+  launch = text[text.index("void launch_fast_humanoid("):].split("\n}\n")[0]
+  assert codegen.QM_HANDOFF_MIN_B == codegen.NT_SV_MIN_B
+  assert (f"const bool ho = mr.qm_handoff > 1 || (mr.qm_handoff == 1 && "
+          f"B >= {codegen.QM_HANDOFF_MIN_B});") in launch
+  picks = re.findall(r"if \((.*)\) \{\n\s+hipLaunchKernelGGL\(\(k_all_humanoid<(\w+), (\w+), (\w+)>\)",
+                     launch)
+  assert len(picks) == 8 and len(set(p[1:] for p in picks)) == 8
+  for i in range(0, 8, 2):         # each variant: the hand-off first, behind `ho`, then without
+    (c1, *v1), (c0, *v0) = picks[i], picks[i + 1]
+    assert v1 == v0[:2] + ["true"] and v0[2] == "false" and c1 == f"ho && ({c0})"
+  # a model where nothing is handed launches the HO = false kernels only
+  off = codegen.generate(m, "humanoid", handoff=False)
+  assert not re.search(r"k_all_humanoid<\w+, \w+, true>", off)
+  # a run-time code object: one kernel, the hand-off compiled in, its count as a global
+  rt = codegen.generate(m, "rt_x", extern_c=True)
+  assert "fast_pos_rt_x<true, false, true>" in rt and "fast_fac_rt_x<true, false, true>" in rt
+  assert f"int k_qm_handoff_rt_x = {len(codegen.qm_handoff_plan(m))};" in rt
+
+
+def _host_fields(m, name, q, v, a):
+  """Every mirror field of the host build of fast_body_<name>, as raw bits."""
+  L = cg.build(m, name)
+  L.cg_set_full_blk(-1)
+  o = Oracle(m)
+  cm = host.model_struct(m)
+  B = len(q)
+  sizes = {f.name: f.size(m.sizes) for f in fields.DATA_FIELDS}
+  out = np.zeros(sum(sizes.values()) * B)
+  q, v, a = (np.ascontiguousarray(x) for x in (q, v, a))
+  cmode = codegen.CONSTRAINT_MODES[codegen.constraint_mode(m)]
+  L.cg_run(ctypes.byref(cm), B, q.ctypes.data, v.ctypes.data, a.ctypes.data, out.ctypes.data,
+           o.efc.capacity, 0, cmode)
+  res, off = {}, 0
+  for f in fields.DATA_FIELDS:
+    res[f.name] = out[off:off + B * sizes[f.name]].view(np.uint64).reshape(B, sizes[f.name])
+    off += B * sizes[f.name]
+  return res
+
+
+@pytest.mark.parametrize("name,B", [("humanoid", 130), ("inertia", 5)])
+def test_host_build_on_off_bit_identical(name, B, monkeypatch):
+  """130 humanoid states: two full 64-lane blocks and a partial one, limit-active ones among
+  them (the work-list path)."""
+  m = models.load(name, disable_contact=True)
+  q, v, a = sample_states(m, B, first=5000, margin=-0.1, resample_tendons=False)
+  assert "handQM" in codegen.generate(m, f"{name}_ho")
+  on = _host_fields(m, f"{name}_ho", q, v, a)
+  monkeypatch.setattr(codegen, "QM_HANDOFF", False)
+  assert "handQM" not in codegen.generate(m, f"{name}_hooff")
+  off = _host_fields(m, f"{name}_hooff", q, v, a)
+  assert on["qM"].any() and on["qLD"].any()
+  for f in fields.DATA_FIELDS:
+    assert np.array_equal(on[f.name], off[f.name]), f.name

@@ -16,7 +16,8 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-OUT = os.path.join(ROOT, "tools", "exp_lib", "variants")
+# VARIANT_DIR: where the code objects go and are run from (default tools/exp_lib/variants)
+OUT = os.environ.get("VARIANT_DIR") or os.path.join(ROOT, "tools", "exp_lib", "variants")
 
 # name -> codegen attribute overrides
 VARIANTS = {
@@ -24,6 +25,9 @@ VARIANTS = {
     "every_reread_temporal": {"NT_TEMPORAL": {"qM", "cdof", "cinert", "qacc", "qfrc_passive",
                                               "qpos", "qvel", "ten_length"}},
     "va_nt_loads": {"NT_LOAD_STAGES": ("va",)},
+    # the qM hand-off (control hands the first-produced rows): off, and the last-produced rows
+    "qm_handoff_off": {"QM_HANDOFF": False},
+    "qm_order_late": {"QM_ORDER": "late"},
 }
 
 
