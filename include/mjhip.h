@@ -341,10 +341,7 @@ MJHIP_API int mjhip_contextLoadKernel(mjhipContext* c, const void* image, size_t
                                       int cmode);
 /* kernels the context's last batched mj_inverseSkip ran on: 0 the generic kernel, 1 the
  * straight-line pipeline (skipstage NONE), 2 the straight-line mj_inverseSkip(POS / VEL)
- * kernels (k_va / k_acc of the model's generated code), 3 the straight-line pipeline of a
- * contact model split over two streams (position stage, then the cooperative constraint
- * kernel beside the fac / va stages, joined by the assembly; opt-in with MJHIP_SPLIT=1);
- * -1 before any call */
+ * kernels (k_va / k_acc of the model's generated code); -1 before any call */
 MJHIP_API int mjhip_contextLastPath(const mjhipContext* c);
 /* Model-constant output slots. Some mjData outputs of a straight-line kernel are numbers its
  * generator holds as literals (the world body's frame, fixed-tendon Jacobians, joint

@@ -130,10 +130,6 @@ NT_LOAD_STAGES = ()
 # (profiles/r04/experiments/nt_variants_3.log); below it, and in k_vaskip (whose loads of the
 # centre's fields are shared by 54 perturbations), they stay temporal
 NT_LOAD_SV_STAGES = ("va",)
-# k_fdall: polls of a centre block's flag before a skip wave gives up (each poll sleeps
-# 8 x 64 cycles; 2^22 polls is about a second -- the flag is raised within the launch's
-# first hundred microseconds, as every centre block is dispatched before any waiting one)
-FD_WAIT_ITERS = 1 << 22
 # Stores whose value is a model constant -- a number this generator holds and prints as a
 # literal, the same in every instance and every call -- leave the stage bodies for
 # fast_const_<name>, which k_const_<name> runs once per context over the whole capacity (and
@@ -151,8 +147,10 @@ CONST_ONCE = True
 # instantiation of the stage bodies drops them (if constexpr), and the k_all kernel launched
 # when Mirror::fd_elide is set runs it on those blocks and the plain bodies on the centres'
 # (one wave-uniform branch at the top); k_vaskip has the FD bodies only. Every other launch is
-# the plain kernel. The arithmetic is the plain kernel's, so every result is the full
-# pipeline's bit for bit (test_inverse_fd_stage_skip_bit_exact). Measured (28,672 instances of
+# the plain kernel. The operations are the plain kernel's, but without the stores the compiler
+# contracts a few multiply-adds differently, so a result can differ from the full pipeline's
+# by a few ulp of qfrc_inverse (test_inverse_fd_stage_skip_bit_exact holds the Jacobians to 16
+# ulp of the largest |qfrc_inverse| over eps). Measured (28,672 instances of
 # the humanoid, mjd_inverseFD's position stage): 134.6 us storing everything, 126.6 us with
 # streaming stores into a shared sink (a streaming store reaches memory wherever it points),
 # 125.4 us with temporal stores into it, 148 us skipping each store behind a wave-uniform
@@ -187,13 +185,6 @@ def _elide_stores(body: str, elided) -> str:
       return line
     return f"{mt.group(1)}if constexpr (!FD) {{ {mt.group(2)} }}"
   return "\n".join(one(x) for x in body.split("\n"))
-
-
-def fdall_ok(m) -> bool:
-  """The model gets k_fdall (mjd_inverseFD layout 1 in one launch): it has k_vaskip and the
-  stage bodies index their LDS by a 64-lane block."""
-  return constraint_mode(m) in ("none", "list") and ALL_LANES == 64 and \
-      all(n == 64 for n in LANES.values())
 
 
 def _ll(st):
@@ -1647,7 +1638,6 @@ def _gen_acc(M: _Model, store_fields=None) -> str:
   same operations as the va stage's second recursion, so the result is its bit for bit. An
   instance with rows (work-list models) stores the raw RNE for the rows pass (k_skip_rows)."""
   G = _Stage(M, store_fields)
-  M.acc_stored = G.stored
   E, m = G.E, M.m
   nv = M.nv
   G.prologue()
@@ -2008,52 +1998,6 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
   if (range) {{ blk0 = range[0] >> 6; B = range[1]; }}
   MJH_PHASE0(19, 27);
 """ + all_calls + "\n" + fuse_tail + "}")
-  # the split launch of a model whose constraint rows serve every instance (contacts): the
-  # position stage alone (k_spos), then the fac and va stages (k_sfv), so that the
-  # cooperative constraint kernel -- which reads only position-stage outputs and the inputs
-  # -- runs on a second stream beside k_sfv, and the assembly kernel (mjhip.hip k_assemble)
-  # joins them (mjhip.hip launch_inverse). Same stage bodies as k_all, so the same results.
-  if M.cmode == "all" and not extern_c:
-    pos_args = _SIG["pos"][1].replace("trig, qo_lds", "trig, nullptr")
-    out.append(f"""template <bool SV>
-__global__ __launch_bounds__(64, 1) void k_spos_{name}(Mirror mr, int B,
-    const double* __restrict__ qpos_in, const double* __restrict__ qvel_in,
-    const double* __restrict__ qacc_in, int* __restrict__ worklist,
-    int* __restrict__ worklist_count, int* __restrict__ worklist_next,
-    int* __restrict__ efc_count) {{
-  __shared__ double trig[{_lds_doubles(m, 0, 64)[0]}];
-  MJH_PHASE0(19, 27);
-  fast_pos_{name}<SV>(mr, blockIdx.x, threadIdx.x, B, {pos_args});
-}}
-template <bool SV>
-__global__ __launch_bounds__(64, 1) void k_sfv_{name}(Mirror mr, int B,
-    double* __restrict__ qfrc_out, int* __restrict__ status, int* __restrict__ efc_count) {{
-  __shared__ double qo_lds[{nqo}];
-{stk_decl}  MJH_PHASE(20);     // the position span runs from k_spos's start to here (launch gap included)
-  fast_fac_{name}<SV>(mr, blockIdx.x, threadIdx.x, B, efc_count, nullptr, nullptr);
-  asm volatile("" ::: "memory"); MJH_SCHED_FENCE(); MJH_PHASE(21);
-  fast_va_{name}<SV>(mr, blockIdx.x, threadIdx.x, B, qfrc_out, status, efc_count, qo_lds,
-                     {stk_arg});
-  asm volatile("" ::: "memory"); MJH_SCHED_FENCE(); MJH_PHASE(22);
-}}
-{"" if shared else "static "}void launch_split_{name}(hipStream_t s, const Mirror& mr, int B, int part,
-    const double* qpos_in, const double* qvel_in, const double* qacc_in, int* status,
-    int* worklist_next, int* efc_count) {{
-  const dim3 g((B + 63) / 64), b(64);
-  if (part == 0) {{
-    if (B >= {NT_SV_MIN_B}) {{
-      hipLaunchKernelGGL(k_spos_{name}<true>, g, b, 0, s, mr, B, qpos_in, qvel_in, qacc_in,
-                         nullptr, nullptr, worklist_next, efc_count);
-    }} else {{
-      hipLaunchKernelGGL(k_spos_{name}<false>, g, b, 0, s, mr, B, qpos_in, qvel_in, qacc_in,
-                         nullptr, nullptr, worklist_next, efc_count);
-    }}
-  }} else if (B >= {NT_SV_MIN_B}) {{
-    hipLaunchKernelGGL(k_sfv_{name}<true>, g, b, 0, s, mr, B, nullptr, status, efc_count);
-  }} else {{
-    hipLaunchKernelGGL(k_sfv_{name}<false>, g, b, 0, s, mr, B, nullptr, status, efc_count);
-  }}
-}}""")
   # batched mj_inverseSkip(POS / VEL) of a model whose rows serve every instance (contacts):
   # k_va (the staged va kernel) or k_acc store the raw RNE, and k_skip_rows (mjhip.hip)
   # finishes every instance -- the previous call's rows (referenceConstraint for POS,
@@ -2089,8 +2033,8 @@ __global__ __launch_bounds__(64, 1) void k_sfv_{name}(Mirror mr, int B,
   # perturbations (engine_derivative_fd.c:646-699). Instance off + t reads every position-
   # stage output (the va pointers it never stores) from its centre instance
   # (t / per)*sstride, which ran the full kernel; its own qvel/qacc and every field the stage
-  # stores stay its own. Skipped stages see unchanged inputs, so the result is the full
-  # pipeline's bit for bit. Work-list models: a centre with limit rows sets *needfull, and
+  # stores stay its own. Skipped stages see unchanged inputs, so the operations are the full
+  # pipeline's (the results within the contraction bound, FD_KEEP above). Work-list models: a centre with limit rows sets *needfull, and
   # k_fd_gate (mjhip.hip) then opens the range of a second k_all over the qvel/qacc
   # perturbations, which runs their full pipeline.
   if M.cmode in ("none", "list") and not extern_c:
@@ -2122,9 +2066,7 @@ __global__ __launch_bounds__(64, 1) void k_sfv_{name}(Mirror mr, int B,
                f"int slane, int B, const int* __restrict__ ecs, int pa, int pv, double eps, "
                f"{_SIG['va'][0]}) {{\n{skip_body}\n}}\n")
   if M.cmode in ("none", "list") and not extern_c:
-    # the acceleration stage alone (mj_inverseSkip(mjSTAGE_VEL)): k_acc for batched calls, and
-    # in k_fdskip for mjd_inverseFD's qacc perturbations, whose velocity-stage inputs (cvel,
-    # cdof_dot, qfrc_passive) and position-stage inputs are their centre's
+    # the acceleration stage alone (mj_inverseSkip(mjSTAGE_VEL)): k_acc for batched calls
     import re
     ab = _gen_acc(M)
     if NT_STORES:
@@ -2133,21 +2075,8 @@ __global__ __launch_bounds__(64, 1) void k_sfv_{name}(Mirror mr, int B,
                              f"{mt.group(4)});", ab, flags=re.M)
     out.append(f"MJH_HD void fast_acc_{name}(const Mirror& mr, int blk, int lane, int B, "
                f"{_SIG['va'][0]}) {{\n{ab}\n}}\n")
-    own_acc = set(M.acc_stored)          # qacc from the centre, perturbed at pa
-    acc_skip = re.sub(r"(double\* __restrict__ P_(\w+) = mr\.\w+ \+ \(\(long\))blk(\*\d+\)\*64 \+ )lane;",
-                      lambda mt: mt.group(0) if mt.group(2) in own_acc else
-                      f"{mt.group(1)}sblk{mt.group(3)}slane;", ab)
-    acc_skip = acc_skip.replace("const bool cflag = ec[0] != 0;", "const bool cflag = ecs[0] != 0;")
-    acc_skip = _perturb_loads(acc_skip, {"qacc": "pa"})
-    out.append(f"MJH_HD void fast_accskip_{name}(const Mirror& mr, int blk, int lane, int sblk, "
-               f"int slane, int B, const int* __restrict__ ecs, int pa, double eps, "
-               f"{_SIG['va'][0]}) {{\n{acc_skip}\n}}\n")
   if M.cmode in ("none", "list") and not extern_c:
     flag = ("  if (ecs[0] != 0) needfull[0] = 1;\n" if M.cmode == "list" else "")
-    pos_call = _SIG["pos"][1].replace("worklist_next", "nullptr")
-    fac_call, va_call = _SIG["fac"][1], _SIG["va"][1]
-    linkage_fd = "" if shared else "static "
-    nv = M.nv
     out.append(f"""// layout 1 over [off, B): per = 2nv perturbations per centre, the first nv of qacc, the
 // next nv of qvel (engine_derivative_fd.c:646-699 order)
 __global__ __launch_bounds__(64, 1) void k_vaskip_{name}(Mirror mr, int B, int off,
@@ -2165,112 +2094,6 @@ __global__ __launch_bounds__(64, 1) void k_vaskip_{name}(Mirror mr, int B, int o
 {"" if shared else "static "}void launch_vaskip_{name}(hipStream_t s, const Mirror& mr, int B, int off, int per,
                                 int sstride, int* efc_count, int* needfull, double eps) {{
   hipLaunchKernelGGL(k_vaskip_{name}, dim3((B - off + 63) / 64), dim3(64), 0, s, mr, B, off,
-                     per, sstride, efc_count, needfull, eps);
-}}
-// mjd_inverseFD layout 1 in one launch (k_fdall, opt-in: MJHIP_FD_FUSED=1, measured slower
-// than k_all then k_vaskip): the position-stage instances [0, B) -- the
-// centres, then the qpos perturbations -- run the whole pipeline (FD: elided stores) on the
-// first B/64 blocks, and the 2nv qvel/qacc perturbations per base state [B, ninst) run
-// k_vaskip's va stage on the blocks after them, beside the qpos perturbations instead of
-// after them. A skip lane reads its centre's position-stage outputs, so it first waits for
-// the centre block's flag (flags[block] == epoch), which that block raises after its
-// position stage behind a device-scope fence (its stores are visible on every XCD); the
-// waiting side fences again before its loads. Blocks are dispatched in index order, so
-// every centre block is running before any block that waits; the wait is bounded all the
-// same, and a wave that gives up raises needfull[3] (the host reports it).
-template <bool SV>
-__global__ __launch_bounds__(64, 1) void k_fdall_{name}(Mirror mr, int B, int ninst, int per,
-    double eps, int* __restrict__ worklist, int* __restrict__ worklist_count,
-    int* __restrict__ worklist_next, int* __restrict__ efc_count, int* __restrict__ needfull,
-    int* __restrict__ flags, int epoch) {{
-  __shared__ double trig[{ntrig}];
-  __shared__ double qo_lds[{nqo}];
-  if (worklist_next && blockIdx.x == 0 && threadIdx.x == 0) *worklist_next = 0;
-  const int nblk = B / 64;                  // B: a whole number of waves
-  if ((int)blockIdx.x < nblk) {{
-    const double* qpos_in = nullptr;
-    const double* qvel_in = nullptr;
-    const double* qacc_in = nullptr;
-    double* qfrc_out = nullptr;
-    int* status = nullptr;
-    const int blk = blockIdx.x, lane = threadIdx.x;
-    if (blk < mr.full_blk) {{               // a centre block: every field, position stage out
-      fast_pos_{name}<SV, false>(mr, blk, lane, B, {pos_call});
-      asm volatile("" ::: "memory");
-      __threadfence();
-      if (lane == 0) __hip_atomic_store(flags + blk, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      MJH_SCHED_FENCE();
-      fast_fac_{name}<SV, false>(mr, blk, lane, B, {fac_call});
-      asm volatile("" ::: "memory"); MJH_SCHED_FENCE();
-      fast_va_{name}<SV, false>(mr, blk, lane, B, {va_call});
-    }} else {{
-      fast_pos_{name}<SV, true>(mr, blk, lane, B, {pos_call});
-      asm volatile("" ::: "memory"); MJH_SCHED_FENCE();
-      fast_fac_{name}<SV, true>(mr, blk, lane, B, {fac_call});
-      asm volatile("" ::: "memory"); MJH_SCHED_FENCE();
-      fast_va_{name}<SV, true>(mr, blk, lane, B, {va_call});
-    }}
-    (void)qpos_in; (void)qvel_in; (void)qacc_in; (void)qfrc_out; (void)status;
-    return;
-  }}
-  const long gi = (long)B + (long)(blockIdx.x - nblk)*64 + threadIdx.x;
-  if (gi >= ninst) return;
-  const long si = (gi - B) / per;
-  const int j = (int)((gi - B) % per);
-  for (int it = 0; __hip_atomic_load(flags + (si >> 6), __ATOMIC_RELAXED,
-                                     __HIP_MEMORY_SCOPE_AGENT) != epoch; it++) {{
-    if (it >= {FD_WAIT_ITERS}) {{
-      __hip_atomic_store(needfull + 3, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      break;
-    }}
-    __builtin_amdgcn_s_sleep(8);
-  }}
-  __threadfence();
-  const int* ecs = efc_count + (si >> 6)*4*64 + (si & 63);
-{flag}  fast_vaskip_{name}(mr, (int)(gi >> 6), (int)(gi & 63), (int)(si >> 6), (int)(si & 63), ninst,
-                    ecs, j < {nv} ? j : -1, j < {nv} ? -1 : j - {nv}, eps, nullptr,
-                    nullptr, efc_count, qo_lds, {stk_arg});
-}}
-{linkage_fd}void launch_fdall_{name}(hipStream_t s, const Mirror& mr, int B, int ninst, int per,
-                               double eps, int* worklist, int* worklist_count,
-                               int* worklist_next, int* efc_count, int* needfull, int* flags,
-                               int epoch) {{
-  const dim3 g((unsigned)((ninst + 63) / 64)), b(64);
-  if (B >= {NT_SV_MIN_B}) {{
-    hipLaunchKernelGGL((k_fdall_{name}<true>), g, b, 0, s, mr, B, ninst, per, eps, worklist,
-                       worklist_count, worklist_next, efc_count, needfull, flags, epoch);
-  }} else {{
-    hipLaunchKernelGGL((k_fdall_{name}<false>), g, b, 0, s, mr, B, ninst, per, eps, worklist,
-                       worklist_count, worklist_next, efc_count, needfull, flags, epoch);
-  }}
-}}
-// mjd_inverseFD layout 2 in one launch over [off, B): the nq = (B - off)/2 qvel perturbations
-// (mj_inverseSkip(mjSTAGE_POS): the va stage over the centre's position stage) on the first
-// blocks, the longer waves, then the nq qacc perturbations (mjSTAGE_VEL: the acceleration
-// stage over the centre's position and velocity stages). nq is a multiple of 64, so each wave
-// has one role; the two run side by side instead of as two under-filled launches.
-__global__ __launch_bounds__(64, 1) void k_fdskip_{name}(Mirror mr, int B, int off,
-    int per, int sstride, int* __restrict__ efc_count, int* __restrict__ needfull, double eps) {{
-  __shared__ double qo_lds[{64 * max(M.nv, 1)}];
-{stk_decl}  const long nq = ((long)B - off) / 2;
-  const long t = (long)blockIdx.x*64 + threadIdx.x;
-  if (t >= 2*nq) return;
-  const bool vel = t < nq;
-  const long gi = vel ? off + nq + t : off + (t - nq);
-  const long si = (vel ? t : t - nq) / per * sstride;
-  const int j = (int)((vel ? t : t - nq) % per);
-  const int* ecs = efc_count + (si >> 6)*4*64 + (si & 63);
-{flag}  if (vel) {{
-    fast_vaskip_{name}(mr, (int)(gi >> 6), (int)(gi & 63), (int)(si >> 6), (int)(si & 63), B,
-                      ecs, -1, j, eps, nullptr, nullptr, efc_count, qo_lds, {stk_arg});
-  }} else {{
-    fast_accskip_{name}(mr, (int)(gi >> 6), (int)(gi & 63), (int)(si >> 6), (int)(si & 63), B,
-                       ecs, j, eps, nullptr, nullptr, efc_count, qo_lds, nullptr);
-  }}
-}}
-{"" if shared else "static "}void launch_fdskip_{name}(hipStream_t s, const Mirror& mr, int B, int off, int per,
-                                int sstride, int* efc_count, int* needfull, double eps) {{
-  hipLaunchKernelGGL(k_fdskip_{name}, dim3((B - off + 63) / 64), dim3(64), 0, s, mr, B, off,
                      per, sstride, efc_count, needfull, eps);
 }}
 // batched mj_inverseSkip on the straight-line path: POS runs the va stage (k_va), VEL the
@@ -2441,9 +2264,8 @@ def generate_registries(entries) -> tuple:
                   "const double*, const double*, const double*, double*, int*, int*, int*, "
                   "int*, int*, const int*);")
       if vaskip:
-        for k in ("vaskip", "fdskip"):
-          main.append(f"void launch_{k}_{name}(hipStream_t, const Mirror&, int, int, int, int, "
-                      "int*, int*, double);")
+        main.append(f"void launch_vaskip_{name}(hipStream_t, const Mirror&, int, int, int, int, "
+                    "int*, int*, double);")
       main.append(f"void launch_skip_{name}(hipStream_t, const Mirror&, int, int, double*, "
                   "int*, int*);")
       main.append(f"int lds_fast_{name}();")
@@ -2451,45 +2273,15 @@ def generate_registries(entries) -> tuple:
         main.append(f"void launch_const_{name}(hipStream_t, const Mirror&, int);")
         main.append(f"int const_stores_{name}();")
       main.append(f"int qm_handoff_{name}();")
-      if constraint_mode(m) == "all":
-        main.append(f"void launch_split_{name}(hipStream_t, const Mirror&, int, int, "
-                    "const double*, const double*, const double*, int*, int*, int*);")
-      if fdall_ok(m):
-        main.append(f"void launch_fdall_{name}(hipStream_t, const Mirror&, int, int, int, double, "
-                    "int*, int*, int*, int*, int*, int*, int);")
     else:
       main.append(generate(m, name))
-    fns = ", ".join(f"launch_{k}_{name}" if vaskip else "nullptr" for k in ("vaskip", "fdskip"))
-    split = f"launch_split_{name}" if constraint_mode(m) == "all" else "nullptr"
-    fdall = f"launch_fdall_{name}" if fdall_ok(m) else "nullptr"
+    vaskip_fn = f"launch_vaskip_{name}" if vaskip else "nullptr"
     const = f"launch_const_{name}, const_stores_{name}" if CONST_ONCE else "nullptr, nullptr"
     reg.append(f'  {{0x{fields.model_signature(m):016x}ull, launch_fast_{name}, "{name}", '
-               f'{CONSTRAINT_MODES[constraint_mode(m)]}, {fns}, launch_skip_{name}, {split}, '
-               f'{fdall}, lds_fast_{name}, {const}, qm_handoff_{name}}},')
+               f'{CONSTRAINT_MODES[constraint_mode(m)]}, {vaskip_fn}, launch_skip_{name}, '
+               f'lds_fast_{name}, {const}, qm_handoff_{name}}},')
   main.append("static const FastKernelEntry g_fast_kernels[] = {")
   main.extend(reg)
-  main.append("  {0ull, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, "
-              "nullptr, nullptr, nullptr}};")
+  main.append("  {0ull, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, "
+              "nullptr}};")
   return "\n".join(main) + "\n", "\n".join(exact) + "\n"
-
-
-def generate_registry(entries) -> str:
-  """entries: list of (name, model). Returns the .inc compiled into libmjhip.so."""
-  out = ["// GENERATED by mujoco_inversedynamicstest_amd/codegen.py (build()) -- do not edit.",
-         "// Straight-line mj_inverse kernels for the bundled models + their signatures.", ""]
-  reg = []
-  for name, m in entries:
-    out.append(generate(m, name))
-    sk = constraint_mode(m) in ("none", "list")
-    fns = ", ".join(f"launch_{k}_{name}" if sk else "nullptr" for k in ("vaskip", "fdskip"))
-    split = f"launch_split_{name}" if constraint_mode(m) == "all" else "nullptr"
-    fdall = f"launch_fdall_{name}" if fdall_ok(m) else "nullptr"
-    const = f"launch_const_{name}, const_stores_{name}" if CONST_ONCE else "nullptr, nullptr"
-    reg.append(f'  {{0x{fields.model_signature(m):016x}ull, launch_fast_{name}, "{name}", '
-               f'{CONSTRAINT_MODES[constraint_mode(m)]}, {fns}, launch_skip_{name}, {split}, '
-               f'{fdall}, lds_fast_{name}, {const}, qm_handoff_{name}}},')
-  out.append("static const FastKernelEntry g_fast_kernels[] = {")
-  out.extend(reg)
-  out.append("  {0ull, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, "
-             "nullptr, nullptr, nullptr}};")
-  return "\n".join(out) + "\n"

@@ -30,8 +30,8 @@
 #include "pair_program.h"
 #include "rollout.h"
 // lane-count variants of the cooperative kernel (kern_constraint.hip), measurement only
-extern template __global__ void k_constraint_coop<8, true, false, false>(mjhipModel, Mirror, int, const int*, const int*, const CoopPair*, const mjh::ContactParam*, const unsigned long long*, int, double*, int*, int*);
-extern template __global__ void k_constraint_coop<32, true, false, false>(mjhipModel, Mirror, int, const int*, const int*, const CoopPair*, const mjh::ContactParam*, const unsigned long long*, int, double*, int*, int*);
+extern template __global__ void k_constraint_coop<8, true, false, false>(mjhipModel, Mirror, int, const int*, const int*, const CoopPair*, const mjh::ContactParam*, const unsigned long long*, int, double*, int*);
+extern template __global__ void k_constraint_coop<32, true, false, false>(mjhipModel, Mirror, int, const int*, const int*, const CoopPair*, const mjh::ContactParam*, const unsigned long long*, int, double*, int*);
 #include "post_pass.h"
 
 // Every kernel takes mjhipModel and Mirror by value, and HIP's kernel-argument segment holds
@@ -160,17 +160,11 @@ __global__ void k_from_mirror(const double* __restrict__ src, double* __restrict
 // perturbations nbase + b*nv + i (dof i) -- then from A = nbase*(nv+1) the others,
 // A + b*2nv + (p-1). The centres lead so that they fill whole waves: only their mirror slots
 // keep every field (Mirror::fd_elide, codegen.FD_KEEP).
-// Layout 2 (the qacc perturbations run mj_inverseSkip(mjSTAGE_VEL), the qvel ones
-// mjSTAGE_POS, engine_derivative_fd.c:646-699): the same position-stage block, then the qacc
-// perturbations A + b*nv + (p-1), then the qvel ones A + nbase*nv + b*nv + (p-1-nv), so that
-// each skip kernel covers whole waves of one kind.
 __device__ static inline long fd_inst(int layout, long nbase, long b, int p, int nv) {
   if (!layout) return b*(3*nv + 1) + p;
   if (p == 0) return b;
   if (p > 2*nv) return nbase + b*nv + (p - 2*nv - 1);
-  if (layout == 1) return nbase*(nv + 1) + b*2*nv + (p - 1);
-  if (p <= nv) return nbase*(nv + 1) + b*nv + (p - 1);
-  return nbase*(nv + 1) + nbase*nv + b*nv + (p - 1 - nv);
+  return nbase*(nv + 1) + b*2*nv + (p - 1);
 }
 
 // instances [first, end) of the layout (first a multiple of 64), one block per 64 instances,
@@ -192,16 +186,10 @@ __device__ static inline void fd_bp(int layout, long nbase, long inst, int nv, l
     const long t = inst - nbase;
     *b = t / nv;
     *p = 2*nv + 1 + (int)(t % nv);
-  } else if (layout == 1) {
+  } else {
     const long t = inst - nbase*(nv + 1);
     *b = t / (2*nv);
     *p = 1 + (int)(t % (2*nv));
-  } else {
-    long t = inst - nbase*(nv + 1);
-    const bool vel = t >= nbase*nv;
-    if (vel) t -= nbase*nv;
-    *b = t / nv;
-    *p = 1 + (int)(t % nv) + (vel ? nv : 0);
   }
 }
 
@@ -229,7 +217,6 @@ __global__ __launch_bounds__(64*kExpandWaves) void k_fd_expand(mjhipModel m, Mir
     if (!fdflag[0]) return;
   } else if (fdflag && blockIdx.x == 0 && threadIdx.x == 0) {
     fdflag[0] = 0;                       // k_vaskip raises it later in stream order
-    fdflag[3] = 0;                       // and k_fdall this one, should a wait time out
   }
   for (long blk = first/64 + blockIdx.x; blk*64 < end; blk += gridDim.x) {
   const long inst = blk*64 + lane;
@@ -390,27 +377,6 @@ __global__ void k_fd_diff(mjhipModel m, Mirror mr, int nbase, double eps, int fl
   }
 }
 
-// the mj_inverse assembly of a split launch (k_spos, then k_sfv beside k_constraint_coop on
-// the second stream): qfrc_inverse = rne + ((armature*qacc - passive) - constraint), in the
-// reference's order and with k_constraint_coop's own expression (engine_inverse.c:132-153),
-// the constraint kernel's status bits, and the row-major output through LDS (coalesced)
-// One thread per (instance, dof), block (blk, dof k) over the block's 64 instances: the mirror
-// reads are whole 512-byte lines; the row-major writes of a block land in one 64 nv region.
-__global__ __launch_bounds__(64) void k_assemble(mjhipModel m, Mirror mr, int B,
-                                                 const int* __restrict__ cstat,
-                                                 double* __restrict__ qfrc_out,
-                                                 int* __restrict__ status) {
-  const int nv = m.nv, blk = blockIdx.x / nv, k = blockIdx.x % nv, lane = threadIdx.x;
-  const long inst = (long)blk*64 + lane;
-  if (inst >= B) return;
-  const long e = ((long)blk*nv + k)*64 + lane;       // the mirror's [blk][k][lane] element
-  const double out = mr.qfrc_inverse[e] + (m.dof_armature[k] * mr.qacc[e] -
-                                           mr.qfrc_passive[e] - mr.qfrc_constraint[e]);
-  mr.qfrc_inverse[e] = out;
-  if (qfrc_out) qfrc_out[inst*nv + k] = out;
-  if (k == 0 && status && cstat[inst]) status[inst] |= cstat[inst];
-}
-
 // Batched mj_fwdActuation (mjh::fwdActuation) over the actuator_length, actuator_velocity and
 // actuator_moment already in the mirror: one lane per instance, 64-instance blocks, so a
 // wave's read or write of one component of a mirror field is one 512-byte segment. Optional
@@ -546,8 +512,6 @@ struct mjhipContext_ {
   // rows (k_vaskip), [1..2] the instance range {first, end} the gated k_fd_expand hands to
   // k_all
   int* fdflag = nullptr;
-  int* fdflags = nullptr;                  // k_fdall's centre-block flags (capacity/64)
-  int fd_epoch = 0;                        // the value k_fdall's flags are raised to
   CoopPair* pairs = nullptr;               // static geom-pair program (coop_program)
   mjh::ContactParam* cparams = nullptr;    // each program pair's mj_contactParam
   int* prog_ipair = nullptr;               // each program pair's predefined-pair index or -1
@@ -555,11 +519,6 @@ struct mjhipContext_ {
   int npair = 0;
   bool boxpair = false;                    // a box-box pair is in the program (coop LDS)
   int coop = 16;                           // lanes per instance of k_constraint_coop (0: off)
-  // the split launch (FastKernelEntry.launch_split): the cooperative constraint kernel on a
-  // second stream beside the fac/va stages, joined by k_assemble; created on first use
-  hipStream_t aux = nullptr;
-  hipEvent_t evpos = nullptr, evcon = nullptr;
-  int* cstat = nullptr;                    // the constraint kernel's status bits per instance
   bool spatial = false;                    // spatial tendons: k_tendon_after runs (post_pass.h)
   // a straight-line kernel specialized for this model at run time (mjhip_contextLoadKernel):
   // a gfx950 code object holding extern "C" k_all_<name>; rt.launch stays null
@@ -943,8 +902,8 @@ MJHIP_API int mjhip_contextCreateCapped(const mjhipModel* caller, int device, in
       hipMemset(c->worklist, 0, 2 * sizeof(int)) != hipSuccess) {
     return fail("hipMalloc(worklist)");
   }
-  if (hipMalloc((void**)&c->fdflag, 4 * sizeof(int)) != hipSuccess ||
-      hipMemset(c->fdflag, 0, 4 * sizeof(int)) != hipSuccess) {
+  if (hipMalloc((void**)&c->fdflag, 3 * sizeof(int)) != hipSuccess ||
+      hipMemset(c->fdflag, 0, 3 * sizeof(int)) != hipSuccess) {
     return fail("hipMalloc(FD flag)");
   }
   const char* nofast = getenv("MJHIP_DISABLE_FAST");
@@ -1069,13 +1028,6 @@ MJHIP_API void mjhip_contextFree(mjhipContext* c) {
   const bool detached = !c->tbuf || timers_detach(c) == MJHIP_OK;
   if (g_timed_ctx == c) g_timed_ctx = nullptr;
   if (c->own_stream && c->stream) hipStreamDestroy(c->stream);
-  if (c->aux) {
-    hipStreamSynchronize(c->aux);
-    hipStreamDestroy(c->aux);
-  }
-  if (c->evpos) hipEventDestroy(c->evpos);
-  if (c->evcon) hipEventDestroy(c->evcon);
-  hipFree(c->cstat);
   if (c->ev0) hipEventDestroy(c->ev0);
   if (c->ev1) hipEventDestroy(c->ev1);
   if (c->tev0) hipEventDestroy(c->tev0);
@@ -1085,7 +1037,6 @@ MJHIP_API void mjhip_contextFree(mjhipContext* c) {
   hipFree(c->status);
   hipFree(c->worklist);
   hipFree(c->fdflag);
-  hipFree(c->fdflags);
   hipFree(c->pairs);
   hipFree(c->cparams);
   hipFree(c->prog_ipair);
@@ -1347,23 +1298,6 @@ MJHIP_API int mjhip_contextSetStream(mjhipContext* c, void* stream) {
   return MJHIP_OK;
 }
 
-// the split launch of a contact model is opt-in (MJHIP_SPLIT=1): measured slower than the
-// one-stream path at config 4, kept for the experiment
-static bool split_disabled() {
-  const char* e = getenv("MJHIP_SPLIT");
-  return !(e && e[0] == '1');
-}
-
-// the split launch's second stream, its two events and the status-bit buffer (first use)
-static int split_ready(mjhipContext* c) {
-  if (c->aux) return MJHIP_OK;
-  HIPCHECK(hipMalloc((void**)&c->cstat, sizeof(int)*(size_t)c->capacity));
-  HIPCHECK(hipEventCreateWithFlags(&c->evpos, hipEventDisableTiming));
-  HIPCHECK(hipEventCreateWithFlags(&c->evcon, hipEventDisableTiming));
-  HIPCHECK(hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking));
-  return MJHIP_OK;
-}
-
 // the straight-line path's passes after the constraint part: sensors (and the transmission
 // and energy terms they carry), INVDISCRETE's qacc restore, the status checks; then the
 // work-list counters change hands
@@ -1423,44 +1357,6 @@ static int launch_inverse(mjhipContext* c, int B, const double* qpos, const doub
     const bool discrete = mjh::hasDiscrete(c->hmodel);
     // fused rows whenever nbody allows, INVDISCRETE included (post_pass.h fastFusedOk)
     const bool fused = mjh::fastFusedOk(c->dmodel);
-    if (c->fast->launch_split && !range && fused && c->coop && c->fast->cmode == 2 &&
-        c->con_cap > 0 && !c->spatial && !mjh::hasFluid(c->dmodel) && !discrete &&
-        !split_disabled()) {
-      // rows on every instance: the position stage, then the cooperative constraint kernel
-      // (position-stage outputs and inputs only) on the second stream beside the fac / va
-      // stages, joined by the assembly
-      if (const int rc = split_ready(c)) return rc;
-      c->last_path = 3;
-      const int* wl = c->worklist + 2;
-      c->fast->launch_split(c->stream, c->mirror, B, 0, qpos, qvel, qacc, status, nxt,
-                            c->mirror.efc_count);
-      HIPCHECK(hipGetLastError());
-      HIPCHECK(hipEventRecord(c->evpos, c->stream));
-      // the fac / va stages are queued first: their 64-lane waves need a whole SIMD's
-      // registers, which the constraint kernel's waves would otherwise take
-      c->fast->launch_split(c->stream, c->mirror, B, 1, nullptr, nullptr, nullptr, status, nxt,
-                            c->mirror.efc_count);
-      HIPCHECK(hipGetLastError());
-      HIPCHECK(hipStreamWaitEvent(c->aux, c->evpos, 0));
-#define MJHIP_LAUNCH_COOP_SPLIT(G, X)                                                         \
-      hipLaunchKernelGGL((k_constraint_coop<G, true, false, X>), dim3(coopGrid(B, G, false)),   \
-                         dim3(64), coopLdsBytes(c->dmodel, G, c->efc_cap, c->boxpair,         \
-                                                      c->npair, c->con_cap),                  \
-                         c->aux, c->dmodel, c->mirror, B, wl, (const int*)cnt, c->pairs,      \
-                         c->cparams, c->masks, c->npair, nullptr, nullptr, c->cstat)
-      if (c->boxpair) MJHIP_LAUNCH_COOP_SPLIT(16, true);
-      else if (c->coop == 8) MJHIP_LAUNCH_COOP_SPLIT(8, false);
-      else if (c->coop == 32) MJHIP_LAUNCH_COOP_SPLIT(32, false);
-      else MJHIP_LAUNCH_COOP_SPLIT(16, false);
-#undef MJHIP_LAUNCH_COOP_SPLIT
-      HIPCHECK(hipGetLastError());
-      HIPCHECK(hipEventRecord(c->evcon, c->aux));
-      HIPCHECK(hipStreamWaitEvent(c->stream, c->evcon, 0));
-      hipLaunchKernelGGL(k_assemble, dim3(grid.x*c->hmodel.nv), block, 0, c->stream, c->dmodel,
-                         c->mirror, B, c->cstat, qfrc, status);
-      HIPCHECK(hipGetLastError());
-      return finish_fast(c, B, grid, block, skipsensor, status, false);
-    }
     if (c->fast->launch) {
       c->fast->launch(grid, block, c->stream, c->mirror, B, qpos, qvel, qacc, qfrc, status,
                       c->worklist + 2, cnt, nxt, c->mirror.efc_count, range);
@@ -1499,7 +1395,7 @@ static int launch_inverse(mjhipContext* c, int B, const double* qpos, const doub
                            c->stream,                                                         \
                            c->dmodel, c->mirror, B, wl,                                       \
                            (const int*)cnt, c->pairs, c->cparams, c->masks, c->npair, qfrc,  \
-                           status, nullptr);                                                  \
+                           status);                                                           \
       } while (0)
       if (contact && c->boxpair) {       // the box-box path is compiled in only here
         if (list) MJHIP_LAUNCH_COOP(16, true, true, true);
@@ -2415,30 +2311,26 @@ MJHIP_API int mjhip_inverseFDBatchAct(mjhipContext* c, int B, const mjtNum* qpos
   long ninst = (long)B*P;
   // sensors are skipped when no sensor derivative is asked for (derivative_fd.c:628)
   const int skipsensor = !DsDq && !DsDv && !DsDa;
-  // Stage skipping as the reference's loop does (engine_derivative_fd.c:646-699): the qvel
-  // perturbations run mj_inverseSkip(mjSTAGE_POS), only the generated va stage over their
-  // centre's position-stage outputs, and the qacc ones mjSTAGE_VEL, the acceleration stage
-  // alone over the centre's position and velocity stages (layout 2, k_fdskip; layout 1 runs
-  // both kinds on the va stage, k_vaskip). Skipped stages would see unchanged inputs: layout 1
-  // equals the full pipeline bit for bit; layout 2 is the same arithmetic in a differently
-  // shaped kernel, where the compiler's multiply-add contraction can round a term differently
-  // (a few ulp of qfrc_inverse). Taken only where the straight-line kernel
-  // is the whole pipeline (no post passes, sensors or actuation terms) and the
-  // position-stage block ends on a wave boundary.
-  const long nA = (long)B*(nv + 1), nQ = (long)B*nv;
+  // Stage skipping after the reference's loop (engine_derivative_fd.c:646-699, which runs the
+  // qvel perturbations through mj_inverseSkip(mjSTAGE_POS) and the qacc ones through
+  // mjSTAGE_VEL): layout 1 runs both kinds on the generated va stage alone, over their
+  // centre's position-stage outputs (k_vaskip). The skipped stages would see unchanged inputs,
+  // so the operations are the full pipeline's; the perturbed instances' bodies leave out the
+  // stores nobody reads (codegen.FD_KEEP), which lets the compiler contract a multiply-add
+  // differently, so a term of qfrc_inverse can round differently by a few ulp (held to 16 ulp
+  // of the largest |qfrc_inverse| over eps, test_inverse_fd_stage_skip_bit_exact). Taken only
+  // where the straight-line kernel is the whole pipeline (no post passes, sensors or
+  // actuation terms) and the position-stage block ends on a wave boundary.
+  const long nA = (long)B*(nv + 1);
   const char* noskip = getenv("MJHIP_FD_NOSKIP");
-  const char* accskip = getenv("MJHIP_FD_ACCSKIP");
-  int layout = c->fast && c->fast->launch_vaskip && !(flags & MJHIP_FLAG_GENERIC) &&
-               skipsensor && !flg_actuation && !c->spatial && !mjh::hasFluid(c->hmodel) &&
-               !mjh::hasDiscrete(c->hmodel) && !mjh_needTrnAfter(&c->hmodel) &&
-               !(m.opt.enableflags & mjhipENBL_ENERGY) && nA % 64 == 0 &&
-               !(noskip && noskip[0] == '1') && !(flags & kFlagFDFull);
-  // layout 2 on request (MJHIP_FD_ACCSKIP=1), when the two perturbation blocks are whole waves
-  // each: not the default, as it measured no faster (k_fdskip 62-64 us against k_vaskip's
-  // 56 us over the same 55,296 instances)
-  if (layout && c->fast->launch_fdskip && nQ % 64 == 0 && accskip && accskip[0] == '1') layout = 2;
+  const int layout = c->fast && c->fast->launch_vaskip && !(flags & MJHIP_FLAG_GENERIC) &&
+                     skipsensor && !flg_actuation && !c->spatial &&
+                     !mjh::hasFluid(c->hmodel) && !mjh::hasDiscrete(c->hmodel) &&
+                     !mjh_needTrnAfter(&c->hmodel) &&
+                     !(m.opt.enableflags & mjhipENBL_ENERGY) && nA % 64 == 0 &&
+                     !(noskip && noskip[0] == '1') && !(flags & kFlagFDFull);
   int rc = MJHIP_OK;
-  // a skip layout's perturbed instances store only what a later kernel of this call reads
+  // the skip layout's perturbed instances store only what a later kernel of this call reads
   // (codegen.FD_KEEP): instance blocks past the centres' drop the rest, as the launches below
   // see through the mirror; restored on every return path
   struct ElideGuard {
@@ -2448,66 +2340,27 @@ MJHIP_API int mjhip_inverseFDBatchAct(mjhipContext* c, int B, const mjtNum* qpos
   if (layout) {
     c->mirror.fd_elide = 1;
     c->mirror.full_blk = (B + 63) / 64;
-    // k_fdall, k_vaskip and k_fdskip run generated stage bodies too
+    // k_vaskip runs a generated stage body too
     if (const int rc2 = ensure_const(c)) return rc2;
   }
-  // with a skip layout only the position-stage block is expanded: the skip kernels read their
-  // centre's inputs and perturb them in registers (the fall-back expands the rest, below)
+  // with the skip layout only the position-stage block is expanded: k_vaskip reads its
+  // centre's inputs and perturbs them in registers (the fall-back expands the rest, below)
   const long nexp = layout ? nA : ninst;
   hipLaunchKernelGGL(k_fd_expand, dim3((unsigned)((nexp + 63)/64)), dim3(64*kExpandWaves), 0,
                      c->stream, c->dmodel, c->mirror, B, dq, dv, da, (m.nu ? dc : nullptr),
                      dact, eps, layout, layout ? c->fdflag : nullptr, (long)0, nexp, 0);
   FDCHECK(hipGetLastError(), "k_fd_expand launch");
-  // MJHIP_FD_FUSED=1: layout 1 in one launch (k_fdall) -- measured slower than the two
-  // launches (config 5: 4.81M against 5.13M Jacobian sets/s on one box), kept for
-  // the A/B
-  const char* fusedfd = getenv("MJHIP_FD_FUSED");
-  if (layout == 1 && c->fast->launch_fdall && c->fast->launch && fusedfd && fusedfd[0] == '1') {
-    // one launch (k_fdall): the position-stage instances' full pipeline on the first blocks,
-    // the qvel/qacc perturbations' va stage beside them, each skip wave once its centres'
-    // position stage is out (a work-list model's rows are served after the fall-back, as
-    // below; a model without rows hands the work-list counters on as launch_inverse does)
-    if (!c->fdflags) {
-      const size_t n = (size_t)c->capacity / 64 + 1;
-      FDCHECK(hipMalloc((void**)&c->fdflags, n*sizeof(int)), "hipMalloc(FD flags)");
-      FDCHECK(hipMemset(c->fdflags, 0, n*sizeof(int)), "hipMemset(FD flags)");
-      c->fd_epoch = 0;
-    }
-    if (++c->fd_epoch == 0x7fffffff) {     // flags from 2^31 calls ago could match again
-      FDCHECK(hipMemsetAsync(c->fdflags, 0, ((size_t)c->capacity / 64 + 1)*sizeof(int),
-                             c->stream), "hipMemset(FD flags)");
-      c->fd_epoch = 1;
-    }
-    int* cnt = c->worklist + c->wl_parity;
-    int* nxt = c->worklist + (c->wl_parity ^ 1);
-    c->last_path = 1;
-    c->fast->launch_fdall(c->stream, c->mirror, (int)nA, (int)ninst, 2*nv, eps, c->worklist + 2,
-                          cnt, nxt, c->mirror.efc_count, c->fdflag, c->fdflags, c->fd_epoch);
-    FDCHECK(hipGetLastError(), "k_fdall launch");
-    if (c->fast->cmode != 1) {
-      c->wl_last = c->wl_parity;
-      c->wl_parity ^= 1;
-    }
-  } else if (layout) {
+  if (layout) {
     // the nv+1 position-stage instances of every base state: the full pipeline (a work-list
     // model's rows are served once, after the fall-back below has added its own)
     const bool defer = c->fast->cmode == 1 && c->fast->launch;
     rc = launch_inverse(c, (int)nA, nullptr, nullptr, nullptr, nullptr, mjhipSTAGE_NONE,
                         nullptr, defer ? kFlagDeferRows : 0, skipsensor);
     if (rc) return rc;
-    if (layout == 2) {
-      // the nv qacc perturbations: the acceleration stage over their centre's position and
-      // velocity stages; the nv qvel ones: the va stage over their centre's position stage
-      c->fast->launch_fdskip(c->stream, c->mirror, (int)ninst, (int)nA, nv, 1,
-                             c->mirror.efc_count, c->fdflag, eps);
-    } else {
-      // the 2nv qvel/qacc perturbations: the va stage over their centre's position stage
-      c->fast->launch_vaskip(c->stream, c->mirror, (int)ninst, (int)nA, 2*nv, 1,
-                             c->mirror.efc_count, c->fdflag, eps);
-    }
+    // the 2nv qvel/qacc perturbations: the va stage over their centre's position stage
+    c->fast->launch_vaskip(c->stream, c->mirror, (int)ninst, (int)nA, 2*nv, 1,
+                           c->mirror.efc_count, c->fdflag, eps);
     FDCHECK(hipGetLastError(), "k_vaskip launch");
-  }
-  if (layout) {
     if (c->fast->cmode == 1) {
       // a work-list model whose centre has limit rows: its perturbations need the rows'
       // velocity and acceleration terms, so every qvel/qacc perturbation then runs the full
@@ -2572,16 +2425,7 @@ MJHIP_API int mjhip_inverseFDBatchAct(mjhipContext* c, int B, const mjtNum* qpos
     };
     bool ok = get(DfDq, oq, nn) && get(DfDv, ov, nn) && get(DfDa, oa, nn) && get(DmDq, om, nm) &&
               get(DsDq, sq_, ns) && get(DsDv, sv_, ns) && get(DsDa, sa_, ns);
-    int flags[4] = {0, 0, 0, 0};
-    if (ok && layout) {
-      ok = hipMemcpyAsync(flags, c->fdflag, sizeof(flags), hipMemcpyDeviceToHost,
-                          c->stream) == hipSuccess;
-    }
     FDCHECK(ok ? hipStreamSynchronize(c->stream) : hipErrorUnknown, "FD output download");
-    if (flags[3]) {
-      set_error("mjhip_inverseFDBatch: a k_fdall wave's wait for its centre timed out");
-      return MJHIP_ERR_HIP;
-    }
   }
 #undef FDCHECK
   return MJHIP_OK;

@@ -299,8 +299,7 @@ class InverseEngine:
   @property
   def last_path(self):
     """Kernels of the last batched inverse: 0 generic, 1 straight-line pipeline, 2 the
-    straight-line mj_inverseSkip(POS / VEL) kernels, 3 the straight-line pipeline of a contact
-    model split over two streams."""
+    straight-line mj_inverseSkip(POS / VEL) kernels."""
     return lib().mjhip_contextLastPath(self.ctx)
 
   @property

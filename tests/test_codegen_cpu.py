@@ -406,3 +406,22 @@ def test_invdiscrete_trn_after_generated_bitexact(integ):
   q = rng.uniform(-1, 1, (B, m.nq)) * 0.5
   v, a = rng.normal(size=(B, m.nv)), rng.normal(size=(B, m.nv))
   run_and_compare(m, f"trn_after_{integ}", q, v, a)
+
+
+@pytest.mark.parametrize("name,contacts,kernels", [
+    ("humanoid", False, {"k_pos", "k_fac", "k_va", "k_all", "k_vaskip", "k_acc", "k_const"}),
+    ("humanoid_contact", True, {"k_pos", "k_fac", "k_va", "k_all", "k_acc", "k_const"})])
+def test_generated_kernel_set(name, contacts, kernels):
+  """The __global__ kernels generated for a bundled model are exactly the ones the library
+  launches: the staged and fused pipeline, the constant stores, batched mj_inverseSkip's
+  k_acc, and mjd_inverseFD's k_vaskip where the rows do not serve every instance. The launch
+  experiments that measured slower (the two-stream split, the fused FD launch, FD layout 2;
+  DESIGN.md) are not compiled in."""
+  import re
+  m = models.load("humanoid", disable_contact=not contacts)
+  assert codegen.constraint_mode(m) == ("all" if contacts else "list")
+  text = codegen.generate(m, name)
+  found = set(re.findall(r"__global__[^;{]*?\bvoid (k_\w+)\(", text))
+  assert found == {f"{k}_{name}" for k in kernels}
+  for gone in ("k_spos_", "k_sfv_", "k_fdall_", "k_fdskip_", "fast_accskip_", "launch_split_"):
+    assert gone not in text, gone

@@ -260,18 +260,17 @@ def test_inverse_fd_parity(humanoid):
 @pytest.mark.parametrize("NB,limits", [(1024, "none"), (64, "all"), (64, "some"),
                                        (48, "some"), (3, "none")])
 def test_inverse_fd_stage_skip_bit_exact(humanoid, NB, limits, monkeypatch):
-  """mjd_inverseFD's stage skipping (engine_derivative_fd.c:646-699: the qvel perturbations
-  run mj_inverseSkip(mjSTAGE_POS), the qacc ones mjSTAGE_VEL) against every perturbation
-  through the full pipeline (MJHIP_FD_NOSKIP=1). Layout 1 (both kinds on the va stage over the
-  centre's position-stage outputs; the default runs k_all then k_vaskip, MJHIP_FD_FUSED=1 one
-  launch, k_fdall, whose skip waves wait for their centres' flags; the perturbed instances
-  run the generated bodies without the stores nobody reads, which the compiler contracts
-  into multiply-adds a little differently) equals it within the contraction bound; layout 2
-  (MJHIP_FD_ACCSKIP=1: the qacc perturbations on the acceleration stage alone over the centre's velocity stage,
-  k_fdskip) within it too. NB=1024 takes the skip layouts; with joint limits active on every centre, or on every
-  fifth, the work-list model falls back on the device to the full pipeline over the
-  perturbations; NB=48 puts 16 qpos perturbations in the centres' block (which stores every
-  field); NB=3 (28*3 instances, not a whole wave) never takes them."""
+  """mjd_inverseFD's stage skipping (after engine_derivative_fd.c:646-699, where the qvel
+  perturbations run mj_inverseSkip(mjSTAGE_POS) and the qacc ones mjSTAGE_VEL) against every
+  perturbation through the full pipeline (MJHIP_FD_NOSKIP=1). The skip layout (k_all over the
+  position-stage instances, then k_vaskip: both kinds of perturbation on the va stage over
+  their centre's position-stage outputs; the perturbed instances run the generated bodies
+  without the stores nobody reads, which the compiler contracts into multiply-adds a little
+  differently) equals it within the contraction bound. NB=1024 takes the skip layout; with
+  joint limits active on every centre, or on every fifth, the work-list model falls back on
+  the device to the full pipeline over the perturbations; NB=48 puts 16 qpos perturbations in
+  the centres' block (which stores every field); NB=3 (28*3 instances, not a whole wave)
+  never takes it."""
   q, v, a = sample_states(humanoid, NB, first=300)
   if limits != "none":                  # push a limited hinge past its range
     j = int(np.flatnonzero(np.asarray(humanoid.jnt_limited))[3])
@@ -279,40 +278,33 @@ def test_inverse_fd_stage_skip_bit_exact(humanoid, NB, limits, monkeypatch):
     q[rows, humanoid.jnt_qposadr[j]] = humanoid.jnt_range[j][1] + 0.2
   e = engine.InverseEngine(humanoid, capacity=NB * (3 * humanoid.nv + 1))
   try:
-    got1 = e.inverse_fd(q, v, a, eps=1e-6, dmdq=True)      # layout 1, the default
-    monkeypatch.setenv("MJHIP_FD_FUSED", "1")               # layout 1 in one launch (k_fdall)
-    got1u = e.inverse_fd(q, v, a, eps=1e-6, dmdq=True)
-    monkeypatch.delenv("MJHIP_FD_FUSED")
-    monkeypatch.setenv("MJHIP_FD_ACCSKIP", "1")             # layout 2
-    got = e.inverse_fd(q, v, a, eps=1e-6, dmdq=True)
+    got = e.inverse_fd(q, v, a, eps=1e-6, dmdq=True)       # the skip layout, the default
     monkeypatch.setenv("MJHIP_FD_NOSKIP", "1")
     ref = e.inverse_fd(q, v, a, eps=1e-6, dmdq=True)
   finally:
     e.close()
-  for g, g1, g1u, r in zip(got, got1, got1u, ref):
-    _assert_fd_contraction_close(g1, r)
-    _assert_fd_contraction_close(g1u, r)
-    _assert_fd_contraction_close(g, r)
+  for what, g, r in zip(("DfDq", "DfDv", "DfDa", "DmDq"), got, ref):
+    _assert_fd_contraction_close(g, r, what)
 
 
-def _assert_fd_contraction_close(g, r, eps=1e-6):
-  """A skip layout against the full pipeline: the same operations, but the compiler contracts
-  multiply-adds per kernel body (layout 2's acceleration-only stage; layout 1's perturbed
-  instances, whose bodies drop the stores nobody reads), so a term of qfrc_inverse can round
-  differently by a few ulp; the forward difference scales that by 1/eps. Bound: 16 ulp of the
-  largest |qfrc_inverse| (<= 1e3 on these states) over eps."""
+def _assert_fd_contraction_close(g, r, what="FD output", eps=1e-6):
+  """The skip layout against the full pipeline: the same operations, but the compiler
+  contracts multiply-adds per kernel body (the perturbed instances' bodies drop the stores
+  nobody reads), so a term of qfrc_inverse can round differently by a few ulp; the forward
+  difference scales that by 1/eps. Bound: 16 ulp of the largest |qfrc_inverse| (<= 1e3 on
+  these states) over eps."""
   tol = 16 * np.finfo(float).eps * 1e3 / eps
   err = np.abs(g - r).max()
-  assert err <= tol, f"DfDa layout 2 vs full pipeline {err:.3e} > {tol:.3e}"
+  assert err <= tol, f"{what}: skip layout vs full pipeline {err:.3e} > {tol:.3e}"
 
 
 @pytest.mark.parametrize("name", ["inverse_test", "linear", "inertia"])
 def test_inverse_fd_stage_skip_other_models(name, monkeypatch):
-  """The stage-skip layouts on the other bundled models with a k_vaskip kernel (work-list or
-  row-free): layout 1 device-resident and back to back (no host wait between calls, each call
+  """The stage-skip layout on the other bundled models with a k_vaskip kernel (work-list or
+  row-free): device-resident and back to back (no host wait between calls, each call
   bit-identical to the last) against the full pipeline within the contraction bound (the
-  perturbed instances' bodies without their unread stores), layout 2 (k_fdskip) within it
-  as well, and both against the oracle's serial mjd_inverseFD."""
+  perturbed instances' bodies without their unread stores), and against the oracle's serial
+  mjd_inverseFD."""
   import torch
   m = models.load(name, disable_contact=True, disable_sensor=(name == "linear"))
   NB = 64
@@ -328,15 +320,12 @@ def test_inverse_fd_stage_skip_other_models(name, monkeypatch):
     for o in outs[:-1]:
       for x, y in zip(o[:3], got):
         assert np.array_equal(x.cpu().numpy(), y)
-    monkeypatch.setenv("MJHIP_FD_ACCSKIP", "1")             # layout 2, k_fdskip
-    got2 = e.inverse_fd(q, v, a, eps=1e-6)
     monkeypatch.setenv("MJHIP_FD_NOSKIP", "1")
     ref = e.inverse_fd(q, v, a, eps=1e-6)
   finally:
     e.close()
-  for g, g2, r in zip(got, got2, ref[:3]):
-    _assert_fd_contraction_close(g, r)
-    _assert_fd_contraction_close(g2, r)
+  for what, g, r in zip(("DfDq", "DfDv", "DfDa"), got, ref[:3]):
+    _assert_fd_contraction_close(g, r, what)
   o = Oracle(m)
   for i in range(0, NB, 8):
     o.set_state(q[i], v[i], a[i])

@@ -162,7 +162,7 @@ def test_generated_text(model):
   # only k_all (and the host entry) select the hand-off
   assert text.count(f"fast_pos_{name}<SV, false, HO>") == 1
   assert text.count(f"fast_fac_{name}<SV, false, HO>") == 1
-  for kern in ("k_pos", "k_fac", "k_spos", "k_sfv", "k_fdall", "k_vaskip", "k_fdskip"):
+  for kern in ("k_pos", "k_fac", "k_vaskip"):
     at = text.find(f"void {kern}_{name}(")
     if at >= 0:
       assert not re.search(r"\bHO\b", text[at:].split("\n}\n")[0]), kern
