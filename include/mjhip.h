@@ -488,6 +488,65 @@ MJHIP_API int mjhip_rolloutBatch(mjhipContext* c, int B, int nstep, const mjhipR
                                  const mjhipRolloutOut* out, int flags, int* status,
                                  int* steps_done);
 
+/* Batched mjd_transitionFD (engine_derivative_fd.c:306-595) for constraint-free states: the
+ * finite-differenced linearisation dx' = A dx + B du of mj_step at B base states, dx in the
+ * tangent space [dq | dv | da] (ndx = 2 nv + na). Every evaluation is mj_stepSkip (:120-155)
+ * with the reference's skipstage -- none for a qpos perturbation (mj_integratePos along e_i),
+ * mjSTAGE_POS for qvel, mjSTAGE_VEL for act and ctrl -- and its skipfactor: a skipped stage
+ * and a skipped factorization see the centre evaluation's results. ctrl nudges respect
+ * ctrlrange as :346-391 does (backward at the upper end, a zero row where neither fits).
+ *
+ * Inputs (mjhipTransitionIn): eps, flg_centered, qpos (B x nq), qvel (B x nv), act (B x na)
+ * and ctrl (B x nu) (NULL: zeros), and optional qfrc_applied (B x nv) and xfrc_applied
+ * (B x 6 nbody), held over all evaluations of a base state (NULL: zeros). Outputs
+ * (mjhipTransitionOut): A (B x ndx x ndx) and B (B x ndx x nu), row-major per base state as
+ * the reference returns them; each may be NULL, and a kind nobody needs is not evaluated.
+ * The sensor Jacobians C and D are not built (this path computes no sensors): a non-NULL C or
+ * D is MJHIP_ERR_ARG. Host arrays, or device arrays with MJHIP_FLAG_DEVICE_PTRS; status (B
+ * ints, may be NULL) is always a host array. Both structs carry their own size.
+ *
+ * Capacity: every evaluation has a mirror slot of its own, so the context's capacity must be
+ * at least mjhip_transitionFDSlots() = 64 ceil(B/64) (1 + P), with P = s (2 nv + na) for A
+ * (s = 2 when flg_centered, else 1) plus 2 nu for B (a ctrl column keeps both nudges);
+ * otherwise MJHIP_ERR_CAPACITY. The mirror slots used are overwritten and hold nothing a
+ * later skipstage call may rely on.
+ *
+ * Mocap poses are not an input of the call: as for mjhip_forwardBatch they are the mirror's
+ * mocap_pos / mocap_quat, which mjhip_mirrorUpload sets.
+ * Base state b uses those of mirror instance b in every one of its evaluations; what the
+ * other slots hold is never read, so poses need to be uploaded for instances [0, B) only.
+ *
+ * status[b] is the OR of the status words of all evaluations of base state b (constraint
+ * rows: MJHIP_INST_UNSUPPORTED; a bad qpos / qvel / qacc), in the centre or any perturbation;
+ * when it is nonzero A[b] and B[b] are all zeros and the call returns MJHIP_ERR_INSTANCE.
+ * The RK4 integrator is MJHIP_ERR_MODEL (the reference's mjERROR), and the models
+ * mjhip_forwardBatchEx refuses are refused the same way. The integrator scratch is
+ * mjhip_rolloutBatch's, allocated on first use. */
+typedef struct mjhipTransitionIn_ {
+  int size;                      /* sizeof(mjhipTransitionIn) as the caller compiled it */
+  int flg_centered;
+  mjtNum eps;
+  const mjtNum* qpos;
+  const mjtNum* qvel;
+  const mjtNum* act;
+  const mjtNum* ctrl;
+  const mjtNum* qfrc_applied;
+  const mjtNum* xfrc_applied;
+} mjhipTransitionIn;
+typedef struct mjhipTransitionOut_ {
+  int size;                      /* sizeof(mjhipTransitionOut) as the caller compiled it */
+  int reserved;
+  mjtNum* A;
+  mjtNum* B;
+  mjtNum* C;                     /* must be NULL */
+  mjtNum* D;                     /* must be NULL */
+} mjhipTransitionOut;
+MJHIP_API int mjhip_transitionFDBatch(mjhipContext* c, int B, const mjhipTransitionIn* in,
+                                      const mjhipTransitionOut* out, int flags, int* status);
+/* mirror slots a call over B base states needs (-1: NULL context) */
+MJHIP_API long mjhip_transitionFDSlots(const mjhipContext* c, int B, int want_A, int want_B,
+                                       int flg_centered);
+
 /* copy one mirror field (reference name) of instances [first, first+count) to/from host
  * memory in the reference's per-instance row-major layout (count x fieldSize) */
 MJHIP_API int mjhip_mirrorDownload(mjhipContext* c, const char* field, int first, int count,

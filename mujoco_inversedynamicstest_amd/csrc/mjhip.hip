@@ -29,6 +29,7 @@
 #include "kernels.h"
 #include "pair_program.h"
 #include "rollout.h"
+#include "transition_call.h"
 // lane-count variants of the cooperative kernel (kern_constraint.hip), measurement only
 extern template __global__ void k_constraint_coop<8, true, false, false>(mjhipModel, Mirror, int, const int*, const int*, const CoopPair*, const mjh::ContactParam*, const unsigned long long*, int, double*, int*);
 extern template __global__ void k_constraint_coop<32, true, false, false>(mjhipModel, Mirror, int, const int*, const int*, const CoopPair*, const mjh::ContactParam*, const unsigned long long*, int, double*, int*);
@@ -545,6 +546,9 @@ struct mjhipContext_ {
   // mjhip_rolloutBatch's integrator scratch (csrc/step.h), [capacity/64][k][64]: allocated by
   // the context's first rollout, freed with the context
   double* rollout_scratch = nullptr;
+  // mjhip_transitionFDBatch's next states (TransitionCall::Y), grown on demand
+  double* transition_y = nullptr;
+  size_t transition_y_n = 0;
 };
 
 // 1 when the model has activation states or a muscle gain / bias: only then are the arrays
@@ -1042,6 +1046,7 @@ MJHIP_API void mjhip_contextFree(mjhipContext* c) {
   hipFree(c->prog_ipair);
   hipFree(c->masks);
   hipFree(c->rollout_scratch);
+  hipFree(c->transition_y);
   hipFree(c->mirror_buf);
   hipFree(c->dmodel_buf);
   if (c->rt_module) hipModuleUnload(c->rt_module);
@@ -2004,6 +2009,142 @@ MJHIP_API int mjhip_rolloutBatch(mjhipContext* c, int B, int nstep, const mjhipR
     if (steps_done) {
       HIPCHECK(hipMemcpyAsync(steps_done, dsteps, sizeof(int)*nB, hipMemcpyDeviceToHost,
                               c->stream));
+    }
+  }
+  // host arrays: collect_status synchronizes the stream before the staging buffers go
+  return collect_status(c, B, status, status || !dev);
+}
+
+MJHIP_API long mjhip_transitionFDSlots(const mjhipContext* c, int B, int want_A, int want_B,
+                                       int flg_centered) {
+  if (!c || B < 0) return -1;
+  const long P = mjhip_transitionSlots(&c->hmodel, want_A, want_B, flg_centered);
+  return 64L*((B + 63)/64)*(1 + P);
+}
+
+MJHIP_API int mjhip_transitionFDBatch(mjhipContext* c, int B, const mjhipTransitionIn* in,
+                                      const mjhipTransitionOut* out, int flags, int* status) {
+  if (!in || in->size < (int)sizeof(mjhipTransitionIn)) {
+    set_error("mjhip_transitionFDBatch: mjhipTransitionIn is NULL or its size field (%d) is "
+              "below %d", in ? in->size : 0, (int)sizeof(mjhipTransitionIn));
+    return MJHIP_ERR_ARG;
+  }
+  if (!out || out->size < (int)sizeof(mjhipTransitionOut)) {
+    set_error("mjhip_transitionFDBatch: mjhipTransitionOut is NULL or its size field (%d) is "
+              "below %d", out ? out->size : 0, (int)sizeof(mjhipTransitionOut));
+    return MJHIP_ERR_ARG;
+  }
+  if (out->C || out->D) {
+    set_error("mjhip_transitionFDBatch: the sensor Jacobians C and D are not built (this path "
+              "computes no sensors); pass NULL");
+    return MJHIP_ERR_ARG;
+  }
+  if (!c) {
+    if (mjhip_deviceCount() <= 0) {
+      set_error("mjhip_transitionFDBatch: no HIP device (there is no CPU fallback)");
+      return MJHIP_ERR_NO_DEVICE;
+    }
+    set_error("mjhip_transitionFDBatch: NULL context");
+    return MJHIP_ERR_ARG;
+  }
+  if (B < 0 || !(in->eps > 0) || !in->qpos || !in->qvel) {
+    set_error("mjhip_transitionFDBatch: bad argument (B %d, eps %g, qpos %p, qvel %p)", B,
+              in->eps, (const void*)in->qpos, (const void*)in->qvel);
+    return MJHIP_ERR_ARG;
+  }
+  const mjhipModel& m = c->hmodel;
+  if (m.opt.integrator == mjhipINT_RK4) {
+    set_error("mjhip_transitionFDBatch: RK4 integrator is not supported");
+    return MJHIP_ERR_MODEL;
+  }
+  if (const char* why = actuation_unsupported(m)) {
+    set_error("mjhip_transitionFDBatch: %s is not supported", why);
+    return MJHIP_ERR_MODEL;
+  }
+  const int want_A = out->A != nullptr, want_B = out->B != nullptr && m.nu > 0;
+  const int P = mjhip_transitionSlots(&m, want_A, want_B, in->flg_centered);
+  const long nblk = (B + 63)/64, slots = 64*nblk*(1 + P);
+  if (slots > c->capacity) {
+    set_error("batch %d (%ld evaluation slots) exceeds context capacity %d", B, slots,
+              c->capacity);
+    return MJHIP_ERR_CAPACITY;
+  }
+  if (B == 0) return MJHIP_OK;
+  HIPCHECK(hipSetDevice(c->device));
+  if (!c->rollout_scratch) {
+    const size_t n = (size_t)mjhip_rolloutScratchDoubles(&m) * c->capacity;
+    HIPCHECK(hipMalloc((void**)&c->rollout_scratch, sizeof(double)*(n ? n : 1)));
+  }
+  const size_t nstate = (size_t)m.nq + m.nv + m.na, ndx = 2*(size_t)m.nv + m.na;
+  const size_t ny = (size_t)slots*nstate;
+  if (c->transition_y_n < ny) {
+    HIPCHECK(hipStreamSynchronize(c->stream));
+    HIPCHECK(hipFree(c->transition_y));
+    c->transition_y = nullptr;
+    c->transition_y_n = 0;
+    HIPCHECK(hipMalloc((void**)&c->transition_y, sizeof(double)*ny));
+    c->transition_y_n = ny;
+  }
+  const bool dev = flags & MJHIP_FLAG_DEVICE_PTRS;
+  const size_t nB = (size_t)B;
+  TransitionCall call{};
+  call.scratch = c->rollout_scratch;
+  call.Y = c->transition_y;
+  call.status = c->status;
+  call.cstatus = P ? c->status + 64*nblk : nullptr;
+  call.eps = in->eps;
+  call.B = B;
+  call.nblk = (int)nblk;
+  call.centered = in->flg_centered != 0;
+  call.want_A = want_A;
+  call.want_B = want_B;
+  RolloutTemps tmp;
+  if (dev) {
+    call.qpos = in->qpos;
+    call.qvel = in->qvel;
+    call.act = m.na ? in->act : nullptr;
+    call.ctrl = m.nu ? in->ctrl : nullptr;
+    call.qfrc_applied = in->qfrc_applied;
+    call.xfrc_applied = in->xfrc_applied;
+    call.A = out->A;
+    call.Bm = want_B ? out->B : nullptr;
+  } else {
+    bool ok = true;
+    auto up = [&](const mjtNum* src, size_t n) -> const double* {
+      if (!src || !n) return nullptr;
+      double* p = tmp.get(n);
+      if (!p || hipMemcpyAsync(p, src, sizeof(double)*n, hipMemcpyHostToDevice, c->stream) !=
+                    hipSuccess) {
+        ok = false;
+        return nullptr;
+      }
+      return p;
+    };
+    call.qpos = up(in->qpos, nB*m.nq);
+    call.qvel = up(in->qvel, nB*m.nv);
+    call.act = up(in->act, nB*m.na);
+    call.ctrl = up(in->ctrl, nB*m.nu);
+    call.qfrc_applied = up(in->qfrc_applied, nB*m.nv);
+    call.xfrc_applied = up(in->xfrc_applied, nB*6*m.nbody);
+    if (want_A) ok = (call.A = tmp.get(nB*ndx*ndx)) && ok;
+    if (want_B) ok = (call.Bm = tmp.get(nB*ndx*m.nu)) && ok;
+    if (!ok) {
+      set_error("mjhip_transitionFDBatch: staging the host arrays on the device failed");
+      return MJHIP_ERR_HIP;
+    }
+  }
+  if (mjhip_launchTransition(c->stream, c->dmodel, c->mirror, call, P, c->con_cap > 0)) {
+    set_error("mjhip_transitionFDBatch: kernel launch failed");
+    return MJHIP_ERR_HIP;
+  }
+  if (!dev) {
+    if (want_A) {
+      HIPCHECK(hipMemcpyAsync(out->A, call.A, sizeof(double)*nB*ndx*ndx, hipMemcpyDeviceToHost,
+                              c->stream));
+    }
+    if (want_B) {
+      HIPCHECK(hipMemcpyAsync(out->B, call.Bm, sizeof(double)*nB*ndx*m.nu,
+                              hipMemcpyDeviceToHost, c->stream));
     }
   }
   // host arrays: collect_status synchronizes the stream before the staging buffers go

@@ -1,7 +1,8 @@
 // step.h -- mj_step for constraint-free states: the integrators of engine_forward.c on top of
 // mjh::forwardSkip, restated in the reference's operation order (file:line as in
-// engine_device.h). Included only by kern_step.hip (k_rollout) and, for the host, by
-// tests/step_harness.cpp; engine_device.h and the other hashed headers do not change.
+// engine_device.h). Included only by kern_step.hip (k_rollout), kern_transition.hip
+// (k_transition, through transition.h) and, for the host, by the test harnesses;
+// engine_device.h and the other hashed headers do not change.
 //
 // The integrators' scratch (qH, qHDiagInv, the RK4 stages, and the implicit integrator's
 // qLU / qDeriv / mjd_rne_vel buffers when the mirror does not hold them) is not part of the
@@ -245,9 +246,11 @@ MJH_HD void solveLUSparse(const mjhipModel& m, R res, SP<S> LU, V vec) {
   }
 }
 
-// mj_EulerSkip engine_forward.c:779-830, skipfactor = 0
+// mj_EulerSkip engine_forward.c:779-830. skipfactor: qH / qHDiagInv are not formed; the
+// solve reads the factor sc.qH / sc.qHDiagInv already hold (mj_stepSkip's reuse)
 template <int S>
-MJH_HD void eulerSkip(const mjhipModel& m, const Lane<S>& d, const StepScratch<S>& sc) {
+MJH_HD void eulerSkip(const mjhipModel& m, const Lane<S>& d, const StepScratch<S>& sc,
+                      bool skipfactor = false) {
   const int nv = m.nv;
   SP<S> qacc = sc.tmp;
   int dof_damping = 0;
@@ -262,11 +265,13 @@ MJH_HD void eulerSkip(const mjhipModel& m, const Lane<S>& d, const StepScratch<S
   if (!dof_damping) {
     copy(qacc, d.qacc, nv);
   } else {
-    for (int i = 0; i < m.nC; i++) sc.qH[i] = d.qM[m.mapM2C[i]];
-    for (int i = 0; i < nv; i++) {
-      sc.qH[m.C_rowadr[i] + m.C_rownnz[i] - 1] += m.opt.timestep * m.dof_damping[i];
+    if (!skipfactor) {
+      for (int i = 0; i < m.nC; i++) sc.qH[i] = d.qM[m.mapM2C[i]];
+      for (int i = 0; i < nv; i++) {
+        sc.qH[m.C_rowadr[i] + m.C_rownnz[i] - 1] += m.opt.timestep * m.dof_damping[i];
+      }
+      factorI(m, sc.qH, sc.qHDiagInv);
     }
-    factorI(m, sc.qH, sc.qHDiagInv);
     for (int i = 0; i < nv; i++) qacc[i] = d.qfrc_smooth[i] + d.qfrc_constraint[i];
     solveLD(m, qacc, sc.qH, sc.qHDiagInv);
   }
@@ -287,18 +292,22 @@ MJH_HD void smoothVel(const mjhipModel& m, const Lane<S>& d, bool flg_bias) {
   if (flg_bias) rneVel(m, d);
 }
 
-// mj_implicitSkip engine_forward.c:948-1021, skipfactor = 0
+// mj_implicitSkip engine_forward.c:948-1021. skipfactor: neither qDeriv nor the factor is
+// formed; the solve reads what d.qLU (implicit) or sc.qH / sc.qHDiagInv (implicitfast) hold
 template <int S>
-MJH_HD int implicitSkip(const mjhipModel& m, const Lane<S>& d, const StepScratch<S>& sc) {
+MJH_HD int implicitSkip(const mjhipModel& m, const Lane<S>& d, const StepScratch<S>& sc,
+                        bool skipfactor = false) {
   const int nv = m.nv;
   const double h = m.opt.timestep;
   int status = 0;
   SP<S> qacc = sc.tmp;
   if (m.opt.integrator == mjhipINT_IMPLICIT) {
-    smoothVel(m, d, true);
-    for (int i = 0; i < m.nD; i++) d.qLU[i] = d.qM[m.mapM2D[i]];
-    addToScl(d.qLU, d.qDeriv, -h, m.nD);
-    status |= factorLUSparse(m, d.qLU, sc.rem);
+    if (!skipfactor) {
+      smoothVel(m, d, true);
+      for (int i = 0; i < m.nD; i++) d.qLU[i] = d.qM[m.mapM2D[i]];
+      addToScl(d.qLU, d.qDeriv, -h, m.nD);
+      status |= factorLUSparse(m, d.qLU, sc.rem);
+    }
     // qfrc = qfrc_smooth + qfrc_constraint (held in qforce: res and vec are distinct arrays)
     for (int i = 0; i < nv; i++) d.qforce[i] = d.qfrc_smooth[i] + d.qfrc_constraint[i];
     solveLUSparse(m, qacc, d.qLU, d.qforce);
@@ -306,16 +315,18 @@ MJH_HD int implicitSkip(const mjhipModel& m, const Lane<S>& d, const StepScratch
     // MhB = qM - h*qDeriv[mapD2M], moved through mapM2C: entry (r, c) of the C sparsity is
     // M's entry of dof r and its ancestor c, and mapD2M's image of it is dAdr(m, r, c)
     const bool stored = stepFluidDeriv(&m);
-    if (stored) smoothVel(m, d, false);
-    for (int r = 0; r < nv; r++) {
-      const int adr = m.C_rowadr[r];
-      for (int k = 0; k < m.C_rownnz[r]; k++) {
-        const int c = m.C_colind[adr + k];
-        const double q = stored ? (double)d.qDeriv[dAdr(m, r, c)] : qDerivAt(m, d, r, c);
-        sc.qH[adr + k] = d.qM[m.mapM2C[adr + k]] + q * -h;
+    if (!skipfactor) {
+      if (stored) smoothVel(m, d, false);
+      for (int r = 0; r < nv; r++) {
+        const int adr = m.C_rowadr[r];
+        for (int k = 0; k < m.C_rownnz[r]; k++) {
+          const int c = m.C_colind[adr + k];
+          const double q = stored ? (double)d.qDeriv[dAdr(m, r, c)] : qDerivAt(m, d, r, c);
+          sc.qH[adr + k] = d.qM[m.mapM2C[adr + k]] + q * -h;
+        }
       }
+      factorI(m, sc.qH, sc.qHDiagInv);
     }
-    factorI(m, sc.qH, sc.qHDiagInv);
     for (int i = 0; i < nv; i++) qacc[i] = d.qfrc_smooth[i] + d.qfrc_constraint[i];
     solveLD(m, qacc, sc.qH, sc.qHDiagInv);
   }
@@ -406,6 +417,26 @@ MJH_HD int step(const mjhipModel& m, const Lane<S>& d, const StepScratch<S>& sc,
   case mjhipINT_EULER: eulerSkip(m, d, sc); break;
   case mjhipINT_RK4: st |= rungeKutta4<S, CONTACT>(m, d, sc); break;
   default: st |= implicitSkip(m, d, sc); break;
+  }
+  return st;
+}
+
+// mj_stepSkip engine_derivative_fd.c:120-155 for a constraint-free state (no fwd/inv check):
+// forwardSkip(skipstage) with step's stop rule, then Euler with skipfactor = skipstage >= POS
+// or implicit / implicitfast with skipfactor = skipstage >= VEL. The stages skipped and the
+// factor reused are whatever d's and sc's pointers of those fields address (transition.h
+// points them at the centre evaluation's). RK4 ignores skipstage in the reference and
+// mjd_transitionFD refuses it; the entry point does too, and a lane that got here anyway is
+// flagged and not advanced.
+template <int S, bool CONTACT>
+MJH_HD int stepSkip(const mjhipModel& m, const Lane<S>& d, const StepScratch<S>& sc,
+                    int skipstage) {
+  int st = forwardSkip<S, CONTACT>(m, d, skipstage);
+  if (st & kStepStop) return st;
+  switch (m.opt.integrator) {
+  case mjhipINT_EULER: eulerSkip(m, d, sc, skipstage >= mjhipSTAGE_POS); break;
+  case mjhipINT_RK4: st |= MJHIP_INST_UNSUPPORTED; break;
+  default: st |= implicitSkip(m, d, sc, skipstage >= mjhipSTAGE_VEL); break;
   }
   return st;
 }

@@ -74,6 +74,9 @@ SIGNATURES = {
                                             _I]),
     "mjhip_rolloutBatch": (ctypes.c_int, [_V, ctypes.c_int, ctypes.c_int, _V, _V, ctypes.c_int,
                                           _V, _V]),
+    "mjhip_transitionFDBatch": (ctypes.c_int, [_V, ctypes.c_int, _V, _V, ctypes.c_int, _V]),
+    "mjhip_transitionFDSlots": (ctypes.c_long, [_V, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_int]),
     "mjhip_mirrorDownload": (ctypes.c_int, [_V, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
                                             _D]),
     "mjhip_mirrorUpload": (ctypes.c_int, [_V, ctypes.c_char_p, ctypes.c_int, ctypes.c_int,
@@ -137,6 +140,19 @@ class RolloutOut(ctypes.Structure):
   """mjhipRolloutOut."""
   _fields_ = [("size", ctypes.c_int), ("reserved", ctypes.c_int), ("state", _V), ("qacc", _V),
               ("fwdinv", _V)]
+
+
+class TransitionIn(ctypes.Structure):
+  """mjhipTransitionIn."""
+  _fields_ = [("size", ctypes.c_int), ("flg_centered", ctypes.c_int), ("eps", ctypes.c_double),
+              ("qpos", _V), ("qvel", _V), ("act", _V), ("ctrl", _V), ("qfrc_applied", _V),
+              ("xfrc_applied", _V)]
+
+
+class TransitionOut(ctypes.Structure):
+  """mjhipTransitionOut."""
+  _fields_ = [("size", ctypes.c_int), ("reserved", ctypes.c_int), ("A", _V), ("B", _V),
+              ("C", _V), ("D", _V)]
 
 
 # the reference's mjtTimer slots (include/mujoco/mjdata.h), mjhipTimer in include/mjhip.h
@@ -487,6 +503,86 @@ class InverseEngine:
     res = self.rollout(qpos, qvel, 1, **kw)
     drop = lambda a: a[:, 0] if a.ndim >= 2 and a.dtype == np.float64 else a
     return drop(res) if isinstance(res, np.ndarray) else tuple(drop(a) for a in res)
+
+  def transition_slots(self, B, want_A=True, want_B=True, centered=False):
+    """Mirror slots (context capacity) transition_fd needs for B base states."""
+    return lib().mjhip_transitionFDSlots(self.ctx, int(B), int(want_A), int(want_B),
+                                         int(centered))
+
+  def transition_fd(self, qpos, qvel, ctrl=None, act=None, eps=1e-6, centered=False,
+                    qfrc_applied=None, xfrc_applied=None, want_A=True, want_B=True,
+                    status=False):
+    """Batched mjd_transitionFD (mjhip_transitionFDBatch) for constraint-free states: the
+    linearisation dx' = A dx + B du of mj_step at each base state. qpos [B, nq], qvel [B, nv],
+    ctrl [B, nu], act [B, na] (None: zeros); qfrc_applied [B, nv] and xfrc_applied
+    [B, 6 nbody] are held over a base state's evaluations (None: zeros). Returns (A
+    [B, ndx, ndx], B [B, ndx, nu]) with ndx = 2 nv + na, None for one not wanted, and the
+    status words [B] after them with status=True. A base state any of whose evaluations has
+    constraint rows or a bad qpos / qvel / qacc has that in its status word and zero
+    matrices. The context's capacity must cover transition_slots(B, ...); the mirror slots
+    are overwritten.
+
+    Host arrays in -> numpy arrays out. Contiguous float64 torch tensors on the context's
+    GPU in -> torch tensors out on that GPU, asynchronous on the context's stream (the status
+    words are then read back only with status=True, which waits for the call)."""
+    m = self.m
+    nv, nq, na, nu, nx = self.nv, self.nq, m.na, m.nu, 6 * m.nbody
+    ndx = 2 * nv + na
+    dev = _dptr(qpos) is not None
+    tin, tout = TransitionIn(), TransitionOut()
+    tin.size, tout.size = ctypes.sizeof(TransitionIn), ctypes.sizeof(TransitionOut)
+    tin.eps, tin.flg_centered = float(eps), int(bool(centered))
+    opt = (("ctrl", ctrl, nu), ("act", act, na), ("qfrc_applied", qfrc_applied, nv),
+           ("xfrc_applied", xfrc_applied, nx))
+    if dev:
+      import torch
+      B = qpos.shape[0]
+      # the kernels index these by B without bounds: check the shapes before the launch
+      if tuple(qpos.shape) != (B, nq) or _dptr(qvel) is None or tuple(qvel.shape) != (B, nv):
+        raise MJHIPError(f"transition_fd: expected qpos [{B}, {nq}] and qvel [{B}, {nv}]")
+      tin.qpos, tin.qvel = _dptr(qpos), _dptr(qvel)
+      for name, arr, n in opt:
+        if arr is None or not n:
+          continue
+        if _dptr(arr) is None or arr.numel() != B * n:
+          raise MJHIPError(f"transition_fd: {name} must be a device tensor of B x {n} = "
+                           f"{B * n} values")
+        setattr(tin, name, _dptr(arr))
+      mk = lambda n: torch.empty((B, ndx, n), dtype=torch.float64, device=qpos.device)
+      A = mk(ndx) if want_A else None
+      Bm = mk(nu) if want_B else None
+      tout.A = None if A is None else _dptr(A)
+      tout.B = None if Bm is None or not nu else _dptr(Bm)
+      st = np.zeros(B, dtype=np.int32) if status else None
+      with _TorchOrder(self):
+        rc = lib().mjhip_transitionFDBatch(self.ctx, B, ctypes.byref(tin), ctypes.byref(tout),
+                                           FLAG_DEVICE_PTRS,
+                                           None if st is None else st.ctypes.data)
+    else:
+      qpos = np.ascontiguousarray(qpos, dtype=np.float64).reshape(-1, nq)
+      B = qpos.shape[0]
+      qvel = np.ascontiguousarray(qvel, dtype=np.float64)
+      if qvel.size != B * nv:
+        raise MJHIPError(f"transition_fd: qvel holds {qvel.size} values, expected {B}x{nv}")
+      tin.qpos, tin.qvel = qpos.ctypes.data, qvel.ctypes.data
+      keep = [qpos, qvel]
+      for name, arr, n in opt:
+        if arr is None or not n:
+          continue
+        arr = np.ascontiguousarray(arr, dtype=np.float64)
+        if arr.size != B * n:
+          raise MJHIPError(f"transition_fd: {name} holds {arr.size} values, expected {B}x{n}")
+        setattr(tin, name, arr.ctypes.data)
+        keep.append(arr)
+      A = np.zeros((B, ndx, ndx)) if want_A else None
+      Bm = np.zeros((B, ndx, nu)) if want_B else None
+      tout.A = None if A is None else A.ctypes.data
+      tout.B = None if Bm is None or not nu else Bm.ctypes.data
+      st = np.zeros(B, dtype=np.int32)
+      rc = lib().mjhip_transitionFDBatch(self.ctx, B, ctypes.byref(tin), ctypes.byref(tout), 0,
+                                         st.ctypes.data)
+    _check(rc, "mjhip_transitionFDBatch")   # per-instance flags come back in `st`
+    return (A, Bm, st) if status else (A, Bm)
 
   def actuation(self, B=None, ctrl=None, act=None, status=False):
     """Batched mj_fwdActuation over the actuator_length, actuator_velocity and
