@@ -367,6 +367,11 @@ MJHIP_API int mjhip_contextConstLaunches(const mjhipContext* c);
  * kernel this context launches at such batches: 0 with the generic kernel, for a model where
  * no row fits, and with MJHIP_QM_HANDOFF=0. */
 MJHIP_API int mjhip_contextQmHandoff(const mjhipContext* c);
+/* The same kernels forward further rows of qM, the last ones the position stage produces, to
+ * the factorization stage in registers the position stage leaves idle; the same switch and
+ * batch threshold govern both. Returns the doubles per instance forwarded that way, not
+ * counted by mjhip_contextQmHandoff: 0 wherever that returns 0 for the reasons above. */
+MJHIP_API int mjhip_contextQmForward(const mjhipContext* c);
 /* the constraint kernel the context's last straight-line call launched, e.g.
  * "k_constraint_coop<16, false, true, false>" (the work-list kernel of a limits-only model) or
  * "k_constraint<true, true, false>"; "none" when it launched none (profiles name it) */

@@ -80,6 +80,18 @@ VA_RECOMPUTE = False
 # (DESIGN.md §Measurements, round 9).
 QM_HANDOFF = True
 QM_ORDER = "late"
+# QM_FORWARD: the doubles per lane that k_all's pos stage may forward to its fac stage in
+# registers on top of the LDS pool (qm_forward_plan): whole rows from the last-produced one
+# backwards, which appear while pass 2 unwinds and its register demand falls, and which the
+# fac stage's eliminations update from their first step. k_all is allocated the fac stage's
+# registers anyway, so the pos stage leaves that many idle. The budget is the largest for which
+# no HO instantiation of k_all_humanoid has scratch (tools/kernel_resources.py): the humanoid
+# forwards 128 doubles with 0 B; the next whole row (136) brings 20 B, all rows (243) 860 B.
+# 0: none forwarded, the LDS plan alone.
+QM_FORWARD = 128
+# experiment knob: False withholds the LDS pool, so that forwarding works alone (the A/B of
+# the two mechanisms; a model whose every row fits QM_FORWARD then forwards all of them)
+QM_LDS = True
 # batches from which the launch functions pick the HO instantiation by default: the same
 # threshold as SV, for the same reason. Below it L2 is not oversubscribed, the fac stage's
 # re-read of qM is served there, and the hand-off only adds LDS traffic to a latency-bound
@@ -413,19 +425,76 @@ def qm_handoff_plan(m, va_slots=None, order=None) -> dict:
   A handed value stays in its slot until the fac stage, so slots are never reused. A row is
   handed whole or not at all, and a row of constants (dof_simplenum) never. order "early":
   rows in production order, each taken when enough slots are free at its post-visit; "late":
-  from the last-produced row backwards, each preferring the slots released last. Empty when
-  the switch is off or less than one row fits."""
+  from the last-produced row backwards, each preferring the slots released last, and leaving
+  out the rows that are forwarded in registers instead (qm_forward_plan; the two are planned
+  together, _qm_plans). Empty when the switch is off or less than one row fits."""
+  return _qm_plans(m, va_slots, order)[0]
+
+
+def qm_forward_plan(m, va_slots=None) -> dict:
+  """{qM index -> index into the fw array} of the entries k_all's pos stage forwards to its
+  fac stage in registers (QM_FORWARD): whole rows from the last-produced one backwards, never
+  a row of constants, disjoint from qm_handoff_plan(m) -- the two are planned together
+  (_qm_plans). Empty with the hand-off off."""
+  return _qm_plans(m, va_slots, None)[1]
+
+
+def _qm_plans(m, va_slots=None, order=None) -> tuple:
+  """(LDS plan, forward plan) of qm_handoff_plan / qm_forward_plan.
+
+  Order "early" forwards nothing. Otherwise the forwarded set is a suffix of the production
+  order (the rows whose values appear as pass 2 unwinds), and the LDS pool goes to the rows
+  before it. A hinge pair is free only after its body's pre-visit, so pairs of the bodies
+  visited last can hold only rows of the suffix: where rows before the suffix are left
+  without a slot while such slots stay empty, suffix rows move back to them, the
+  earliest-produced (the one that would live in registers longest) first. Of all suffixes
+  whose forwarded doubles stay within QM_FORWARD the one handing the most doubles in total is
+  taken, the shortest among equals: what the LDS pool holds anyway stays there, and registers
+  (whose overflow is scratch, which costs far more than either) take only what it cannot."""
   order = QM_ORDER if order is None else order
   assert order in ("early", "late"), order
   M = m if isinstance(m, _Model) else _Model(m, va_slots, handoff=False)
-  m = M.m
   if not QM_HANDOFF or not FUSE or ALL_LANES > 64:
+    return {}, {}
+  if order == "early" or QM_FORWARD <= 0:
+    return _qm_lds_plan(M, order, ()), {}
+  last_first = [k for _, k in sorted(_qm_produced(M), reverse=True)]
+  best = None
+  for n in range(len(last_first) + 1):
+    suffix = last_first[:n]
+    lds = _qm_lds_plan(M, order, suffix)
+    fwd = [k for k in suffix if M.Madr[k] not in lds]
+    nfwd = sum(len(qm_row(M, k)) for k in fwd)
+    if nfwd <= QM_FORWARD and (best is None or len(lds) + nfwd > best[0]):
+      best = (len(lds) + nfwd, lds, fwd)
+  _, lds, fwd = best
+  entries = sorted(a for k in fwd for a in qm_row(M, k))
+  return lds, {a: i for i, a in enumerate(entries)}
+
+
+def _qm_events(M) -> dict:
+  """{("pre" | "post", body): position} in the pos stage's pass-2 traversal."""
+  events = []
+  M.dfs(lambda b: events.append(("pre", b)), lambda b: events.append(("post", b)))
+  return {ev: t for t, ev in enumerate(events)}
+
+
+def _qm_produced(M) -> list:
+  """[(post-visit that produces it, dof)] of the qM rows that are not rows of constants."""
+  when = _qm_events(M)
+  return [(when[("post", M.dbody[k])], k) for k in range(M.nv) if not M.simplenum[k]]
+
+
+def _qm_lds_plan(M, order, suffix) -> dict:
+  """qm_handoff_plan's slot assignment with the rows of the dofs in `suffix` held back for
+  forwarding: they are offered slots only where a row outside it went without, and after
+  all of those, in production order."""
+  m = M.m
+  if not QM_LDS:
     return {}
   nreg, nqo = _lds_doubles(m, M.va_nslot, 64)
   rows = nreg // 64                     # of the trig/stack region (max(1, ...) // 64 = 0: none)
-  events = []
-  M.dfs(lambda b: events.append(("pre", b)), lambda b: events.append(("post", b)))
-  when = {ev: t for t, ev in enumerate(events)}
+  when = _qm_events(M)
   # slot -> the event after which it is free (-1: from the start of the pos stage)
   free_from = {s: -1 for s in range(2 * len(M.trig), rows)}
   if m.nv > 0:
@@ -434,18 +503,25 @@ def qm_handoff_plan(m, va_slots=None, order=None) -> dict:
     for j, h in M.trig.items():
       t = when[("pre", int(m.jnt_bodyid[j]))]
       free_from[2 * h] = free_from[2 * h + 1] = t
-  produced = [(when[("post", M.dbody[k])], k) for k in range(M.nv) if not M.simplenum[k]]
+  held = set(suffix)
+  produced = [x for x in _qm_produced(M) if x[1] not in held]
   produced.sort(reverse=order == "late")
   plan, taken = {}, set()
-  for t, k in produced:
+
+  def offer(t, k):
     entries = qm_row(M, k)
     free = sorted((s for s in free_from if free_from[s] < t and s not in taken),
                   key=lambda s: (free_from[s], s), reverse=order == "late")
     if len(free) < len(entries):
-      continue
+      return False
     for a, s in zip(entries, free):
       plan[a] = s
       taken.add(s)
+    return True
+  left_out = [offer(t, k) for t, k in produced].count(False)
+  if left_out:
+    for t, k in sorted(x for x in _qm_produced(M) if x[1] in held):
+      offer(t, k)
   return plan
 
 
@@ -504,7 +580,8 @@ class _Model:
     self.va_nslot = min(va_slots, depth)
     self.spatial = set(spatial_tendons(m))
     # QM_HANDOFF: {qM index: LDS slot} of the entries the HO instantiation hands on-chip
-    self.handoff = qm_handoff_plan(self) if handoff is None or handoff else {}
+    # QM_FORWARD: {qM index: fw index} of those it forwards in registers instead
+    self.handoff, self.forward = _qm_plans(self) if handoff is None or handoff else ({}, {})
     # CONST_ONCE: {(field, index): expression} in emission order, and the declarations the
     # expressions name
     self.consts, self.const_decls = {}, []
@@ -581,6 +658,14 @@ class _Stage:
       if self.store_fields is None or field in self.store_fields:
         self.E(f"P_qM[{k}*64] = v_;")
       self.E(f"mjh::handQM<HO>({_ho_ref(self.M, self.M.handoff[k], 'pos')}, v_); }}")
+      return
+    if field == "qM" and k in self.M.forward:
+      # a forwarded entry: the plain mirror store (the kernels whose fac stage re-reads it,
+      # and every reader after the call) and the register the fac stage takes it from
+      self.E(f"{{ const double v_ = {expr};")
+      if self.store_fields is None or field in self.store_fields:
+        self.E(f"P_qM[{k}*64] = v_;")
+      self.E(f"if constexpr (HO) fw[{self.M.forward[k]}] = v_; }}")
       return
     if self.store_fields is None or field in self.store_fields:
       self.E(f"P_{field}[{k}*64] = {expr};")
@@ -1214,7 +1299,8 @@ def _gen_fac(M: _Model, store_fields=None) -> str:
   mapM2C = [int(x) for x in m.mapM2C]
   for a in range(m.nM):
     E(f"const double M_{a} = mjh::takeQM<HO>({_ho_ref(M, M.handoff[a], 'fac')}, P_qM + {a}*64);"
-      if a in M.handoff else f"const double M_{a} = P_qM[{a}*64];")
+      if a in M.handoff else f"const double M_{a} = HO ? fw[{M.forward[a]}] : P_qM[{a}*64];"
+      if a in M.forward else f"const double M_{a} = P_qM[{a}*64];")
   E(f"double {', '.join(f'L_{c} = M_{mapM2C[c]}' for c in range(m.nC))};")
   for k in range(nv - 1, -1, -1):
     ra = rowadr[k]
@@ -1803,9 +1889,19 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
   if why:
     raise ValueError(f"model '{name}' cannot use the straight-line kernels: {why}")
   M = _Model(m, va_slots, handoff)
+  # the forwarded qM entries (QM_FORWARD) travel from the pos body to the fac body in a local
+  # array of the caller's, fw: registers once the bodies are inlined into k_all. Every other
+  # caller passes null, and with HO = false neither body touches it.
+  sig = dict(_SIG)
+  nfw = len(M.forward)
+  if nfw:
+    sig["pos"] = (_SIG["pos"][0] + ", double* __restrict__ fw", _SIG["pos"][1] + ", fw")
+    sig["fac"] = (_SIG["fac"][0] + ", const double* __restrict__ fw", _SIG["fac"][1] + ", fw")
+  fw_decl = f"double fw[{nfw}];   // the forwarded qM entries (QM_FORWARD)\n" if nfw else ""
   # the pos and fac bodies' HO argument where the hand-off is on (k_all's kernel template
   # argument, the literal in the host entry and in a run-time code object)
-  ho = {st: "" if not _HO_PARAM[st] else ", true" if M.handoff else ", false" for st in STAGES}
+  ho = {st: "" if not _HO_PARAM[st] else ", true" if M.handoff or M.forward else ", false"
+        for st in STAGES}
   # the region the pos stage's trig and the va stage's cdof stack share, and qo_lds, in
   # doubles per 64 lanes; every wrapper that runs the va body declares the region
   nreg64 = _lds_doubles(m, M.va_nslot, 64)[0]
@@ -1820,7 +1916,8 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
     import re
     # the fac stage's re-reads stay temporal; the other stages' re-reads stream only in the
     # SV = true instantiation of k_all (a batch large enough to oversubscribe L2, NT_SV_MIN_B)
-    reread = set(re.findall(r"= P_(\w+)\[", bodies["fac"])) | ({"qM"} if M.handoff else set())
+    reread = set(re.findall(r"= P_(\w+)\[", bodies["fac"])) | \
+        ({"qM"} if M.handoff or M.forward else set())
     later = set(re.findall(r"= P_(\w+)\[", "\n".join(bodies.values()))) - reread
     if NT_TEMPORAL is not None:
       reread, later = set(NT_TEMPORAL), set()
@@ -1873,7 +1970,7 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
   if exact:   # frames for the native solver: every operation rounded (exact_fp)
     out.append("#if defined(__clang__)\n#pragma clang fp contract(off)\n#endif")
   for st in STAGES:
-    params, args = _SIG[st]
+    params, args = sig[st]
     out.append(f"template <bool SV = true, bool FD = false{_HO_PARAM[st]}>\n"
                f"MJH_HD void fast_{st}_{name}(const Mirror& mr, int blk, int lane, int B, "
                f"{params}) {{\n{bodies[st]}\n}}\n")
@@ -1893,8 +1990,8 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
   double trig[{nreg64}];   // LDS on the device (k_pos's trig, then k_va's cdof stack)
   double qo_lds[{64 * max(M.nv, 1)}];             // LDS on the device (k_va; the qM hand-off)
   const bool fd = mr.fd_elide && blk >= mr.full_blk;   // mjd_inverseFD's perturbed blocks
-""" + const_call + "".join(f"  if (fd) fast_{st}_{name}<true, true{ho[st]}>(mr, blk, lane, B, {_SIG[st][1]});\n"
-              f"  else fast_{st}_{name}<true, false{ho[st]}>(mr, blk, lane, B, {_SIG[st][1]});\n"
+""" + ("  " + fw_decl if nfw else "") + const_call + "".join(f"  if (fd) fast_{st}_{name}<true, true{ho[st]}>(mr, blk, lane, B, {sig[st][1]});\n"
+              f"  else fast_{st}_{name}<true, false{ho[st]}>(mr, blk, lane, B, {sig[st][1]});\n"
               for st in STAGES)
              + (f"""  if (qfrc_out && (long)blk*64 + lane < B) {{
     for (int k = 0; k < {M.nv}; k++) qfrc_out[((long)blk*64 + lane)*{M.nv} + k] = qo_lds[lane*{M.nv} + k];
@@ -1902,14 +1999,15 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
 """ if M.cmode != "all" else "  (void)qo_lds;\n") + "}\n")
   out.append("#if defined(__HIPCC__)")
   for st in STAGES:
-    params, args = _SIG[st]
+    params, args = sig[st]
     tail = ""
     nl = LANES[st]
     sub = 64 // nl    # workgroups per 64-instance block
     if st == "pos":                                # staged: qM goes through the mirror
       params = params.replace(", double* __restrict__ trig", "")
       params = params.replace(", double* __restrict__ qo_lds", "")
-      args = args.replace(", qo_lds", ", nullptr")
+      params = params.replace(", double* __restrict__ fw", "")
+      args = args.replace(", qo_lds", ", nullptr").replace(", fw", ", nullptr")
       decl = f"  __shared__ double trig[{max(1, 2 * len(M.trig) * nl)}];\n"
     elif st == "va":
       params = params.replace(", double* __restrict__ qo_lds", "")
@@ -1929,7 +2027,8 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
     else:
       params = params.replace(", const double* __restrict__ trig", "")
       params = params.replace(", const double* __restrict__ qo_lds", "")
-      args = args.replace(", trig, qo_lds", ", nullptr, nullptr")
+      params = params.replace(", const double* __restrict__ fw", "")
+      args = args.replace(", trig, qo_lds", ", nullptr, nullptr").replace(", fw", ", nullptr")
       decl = ""
     if sub == 1:
       bl = "blockIdx.x, threadIdx.x"
@@ -1977,7 +2076,7 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
 
   def stage_calls(fd, ind="  "):
     return "\n".join(f"{ind}fast_{st}_{name}<{sv}, {fd}{kho[st]}>(mr, {bl}, B, "
-                     f"{_SIG[st][1].replace('worklist_next', 'nullptr')});\n"
+                     f"{sig[st][1].replace('worklist_next', 'nullptr')});\n"
                      f"{ind}asm volatile(\"\" ::: \"memory\"); MJH_SCHED_FENCE(); MJH_PHASE({20 + k});"
                      for k, st in enumerate(STAGES))
   # the FD instantiation (mjd_inverseFD's stage-skip layout): the plain bodies on the centres'
@@ -1997,7 +2096,7 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
   int blk0 = 0;
   if (range) {{ blk0 = range[0] >> 6; B = range[1]; }}
   MJH_PHASE0(19, 27);
-""" + all_calls + "\n" + fuse_tail + "}")
+""" + ("  " + fw_decl if nfw else "") + all_calls + "\n" + fuse_tail + "}")
   # batched mj_inverseSkip(POS / VEL) of a model whose rows serve every instance (contacts):
   # k_va (the staged va kernel) or k_acc store the raw RNE, and k_skip_rows (mjhip.hip)
   # finishes every instance -- the previous call's rows (referenceConstraint for POS,
@@ -2010,7 +2109,7 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
                   lambda mt: f"{mt.group(1)}MJH_NT_STORE(P_{mt.group(2)}[{mt.group(3)}*64], "
                              f"{mt.group(4)});", ab, flags=re.M)
     out.append(f"MJH_HD void fast_acc_{name}(const Mirror& mr, int blk, int lane, int B, "
-               f"{_SIG['va'][0]}) {{\n{ab}\n}}\n")
+               f"{sig['va'][0]}) {{\n{ab}\n}}\n")
     out.append(f"""__global__ __launch_bounds__(64, 1) void k_acc_{name}(Mirror mr, int B,
     double* __restrict__ qfrc_out, int* __restrict__ status, int* __restrict__ efc_count) {{
   fast_acc_{name}(mr, blockIdx.x, threadIdx.x, B, qfrc_out, status, efc_count, nullptr,
@@ -2064,7 +2163,7 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
     skip_body = _perturb_loads(skip_body, {"qvel": "pv", "qacc": "pa"})
     out.append(f"MJH_HD void fast_vaskip_{name}(const Mirror& mr, int blk, int lane, int sblk, "
                f"int slane, int B, const int* __restrict__ ecs, int pa, int pv, double eps, "
-               f"{_SIG['va'][0]}) {{\n{skip_body}\n}}\n")
+               f"{sig['va'][0]}) {{\n{skip_body}\n}}\n")
   if M.cmode in ("none", "list") and not extern_c:
     # the acceleration stage alone (mj_inverseSkip(mjSTAGE_VEL)): k_acc for batched calls
     import re
@@ -2074,7 +2173,7 @@ def generate(m, name: str, store_fields=None, extern_c: bool = False, shared: bo
                   lambda mt: f"{mt.group(1)}MJH_NT_STORE(P_{mt.group(2)}[{mt.group(3)}*64], "
                              f"{mt.group(4)});", ab, flags=re.M)
     out.append(f"MJH_HD void fast_acc_{name}(const Mirror& mr, int blk, int lane, int B, "
-               f"{_SIG['va'][0]}) {{\n{ab}\n}}\n")
+               f"{sig['va'][0]}) {{\n{ab}\n}}\n")
   if M.cmode in ("none", "list") and not extern_c:
     flag = ("  if (ecs[0] != 0) needfull[0] = 1;\n" if M.cmode == "list" else "")
     out.append(f"""// layout 1 over [off, B): per = 2nv perturbations per centre, the first nv of qacc, the
@@ -2140,9 +2239,12 @@ __global__ __launch_bounds__(64, 1) void k_acc_{name}(Mirror mr, int B,
   if extern_c:
     out.append(f'extern "C" __device__ __attribute__((used)) int k_qm_handoff_{name} = '
                f"{len(M.handoff)};")
+    out.append(f'extern "C" __device__ __attribute__((used)) int k_qm_forward_{name} = {nfw};')
   else:
     out.append(f"{'' if shared else 'static '}int qm_handoff_{name}() "
                f"{{ return {len(M.handoff) if FUSE else 0}; }}")
+    out.append(f"{'' if shared else 'static '}int qm_forward_{name}() "
+               f"{{ return {nfw if FUSE else 0}; }}")
   out.append(f"""{"" if shared else "static "}void launch_fast_{name}(dim3 g, dim3 b, hipStream_t s, const Mirror& mr,
     int B, const double* qpos_in, const double* qvel_in, const double* qacc_in, double* qfrc_out,
     int* status, int* worklist, int* worklist_count, int* worklist_next, int* efc_count,
@@ -2158,9 +2260,9 @@ __global__ __launch_bounds__(64, 1) void k_acc_{name}(Mirror mr, int B,
       out.append(f"  const bool ho = mr.qm_handoff > 1 || (mr.qm_handoff == 1 && "
                  f"B >= {QM_HANDOFF_MIN_B});")
       variants = tuple(x for cond, v in variants for x in
-                       ([(f"ho && ({cond})", v[:-1] + ", true>")] if M.handoff else []) +
+                       ([(f"ho && ({cond})", v[:-1] + ", true>")] if M.handoff or M.forward else []) +
                        [(cond, v[:-1] + ", false>")])
-      if not M.handoff:
+      if not (M.handoff or M.forward):
         out.append("  (void)ho;")
     for cond, v in variants:
       out.append(f"  if ({cond}) {{\n    hipLaunchKernelGGL((k_all_{name}{v}), {gb}, 0, s, mr, B, "
@@ -2169,8 +2271,8 @@ __global__ __launch_bounds__(64, 1) void k_acc_{name}(Mirror mr, int B,
   else:   # staged kernels (experiments): the whole [0, B) range only
     out.append("  if (range) return;   // device-side ranges need k_all")
     for st in STAGES:
-      args = _SIG["va"][1].replace(", trig", "").replace(", qo_lds", "") if st == "va" else \
-          _SIG[st][1].replace(", trig, qo_lds", "")
+      args = sig["va"][1].replace(", trig", "").replace(", qo_lds", "") if st == "va" else \
+          sig[st][1].replace(", trig, qo_lds", "")
       gb = "g, b" if LANES[st] == 64 else f"dim3(g.x*{64 // LANES[st]}), dim3({LANES[st]})"
       out.append(f"  hipLaunchKernelGGL(k_{st}_{name}, {gb}, 0, s, mr, B, {args});")
   out.append("}")
@@ -2273,15 +2375,16 @@ def generate_registries(entries) -> tuple:
         main.append(f"void launch_const_{name}(hipStream_t, const Mirror&, int);")
         main.append(f"int const_stores_{name}();")
       main.append(f"int qm_handoff_{name}();")
+      main.append(f"int qm_forward_{name}();")
     else:
       main.append(generate(m, name))
     vaskip_fn = f"launch_vaskip_{name}" if vaskip else "nullptr"
     const = f"launch_const_{name}, const_stores_{name}" if CONST_ONCE else "nullptr, nullptr"
     reg.append(f'  {{0x{fields.model_signature(m):016x}ull, launch_fast_{name}, "{name}", '
                f'{CONSTRAINT_MODES[constraint_mode(m)]}, {vaskip_fn}, launch_skip_{name}, '
-               f'lds_fast_{name}, {const}, qm_handoff_{name}}},')
+               f'lds_fast_{name}, {const}, qm_handoff_{name}, qm_forward_{name}}},')
   main.append("static const FastKernelEntry g_fast_kernels[] = {")
   main.extend(reg)
   main.append("  {0ull, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, "
-              "nullptr}};")
+              "nullptr, nullptr}};")
   return "\n".join(main) + "\n", "\n".join(exact) + "\n"

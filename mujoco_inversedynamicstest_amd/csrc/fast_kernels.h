@@ -39,6 +39,8 @@ struct FastKernelEntry {
   // stage in LDS (codegen.py qm_handoff_plan), launched when Mirror::qm_handoff is set; 0
   // where nothing fits. Null for run-time kernels: the count is a global of the code object
   int (*qm_handoff)();
+  // and those it forwards in registers (codegen.py qm_forward_plan), under the same switch
+  int (*qm_forward)();
 };
 
 // static LDS a k_all workgroup may hold while four of them share a CU's 160 KB

@@ -532,6 +532,7 @@ struct mjhipContext_ {
   hipFunction_t rt_const_fn = nullptr;     // the code object's k_const_<name>
   int rt_nconst = 0;                       // and its k_const_count_<name>
   int rt_nhand = 0;                        // and its k_qm_handoff_<name> (0: none)
+  int rt_nfwd = 0;                         // and its k_qm_forward_<name> (0: none)
   // the model-constant output slots the generated stage bodies leave to k_const may not hold
   // their values: set at creation, by mjhip_contextLoadKernel (another code object carries its
   // own constants) and by every mjhip_mirrorUpload; cleared by ensure_const
@@ -1132,6 +1133,14 @@ MJHIP_API int mjhip_contextLoadKernel(mjhipContext* c, const void* image, size_t
     c->rt_nhand = 0;
     (void)hipGetLastError();
   }
+  const std::string fname = std::string("k_qm_forward_") + name;   // and forwards in registers
+  c->rt_nfwd = 0;
+  if (hipModuleGetGlobal(&nhp, &nhbytes, mod, fname.c_str()) != hipSuccess ||
+      nhbytes != sizeof(int) ||
+      hipMemcpy(&c->rt_nfwd, (const void*)nhp, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) {
+    c->rt_nfwd = 0;
+    (void)hipGetLastError();
+  }
   size_t tbytes = 0;                       // its per-stage timer pointer (MJH_TBUF_EXTERN)
   if (hipModuleGetGlobal(&c->rt_tbuf, &tbytes, mod, "mjh_tbuf") != hipSuccess ||
       tbytes != sizeof(void*)) {
@@ -1250,6 +1259,12 @@ MJHIP_API int mjhip_contextQmHandoff(const mjhipContext* c) {
   if (!c || !c->fast) return 0;
   if (c->fast == &c->rt) return c->rt_nhand;
   return (c->mirror.qm_handoff && c->fast->qm_handoff) ? c->fast->qm_handoff() : 0;
+}
+
+MJHIP_API int mjhip_contextQmForward(const mjhipContext* c) {
+  if (!c || !c->fast) return 0;
+  if (c->fast == &c->rt) return c->rt_nfwd;
+  return (c->mirror.qm_handoff && c->fast->qm_forward) ? c->fast->qm_forward() : 0;
 }
 
 MJHIP_API int mjhip_contextConstLaunches(const mjhipContext* c) {

@@ -62,6 +62,7 @@ SIGNATURES = {
     "mjhip_contextConstStores": (ctypes.c_int, [_V]),
     "mjhip_contextConstLaunches": (ctypes.c_int, [_V]),
     "mjhip_contextQmHandoff": (ctypes.c_int, [_V]),
+    "mjhip_contextQmForward": (ctypes.c_int, [_V]),
     "mjhip_contextConstraintKernel": (ctypes.c_char_p, [_V]),
     "mjhip_contextStream": (_V, [_V]),
     "mjhip_contextSetStream": (ctypes.c_int, [_V, _V]),
@@ -330,6 +331,12 @@ class InverseEngine:
     stage in LDS instead of through the mirror, at batches of 49,152 and more (at every batch
     when MJHIP_QM_HANDOFF=1 was set as the engine was created; 0: none, or it was set to 0)."""
     return lib().mjhip_contextQmHandoff(self.ctx)
+
+  @property
+  def qm_forward(self):
+    """qM entries per instance that the same k_all forwards from its pos stage to its fac stage
+    in registers, on top of qm_handoff and under the same switch and batch threshold."""
+    return lib().mjhip_contextQmForward(self.ctx)
 
   @property
   def const_launches(self):

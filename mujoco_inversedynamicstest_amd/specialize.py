@@ -62,7 +62,10 @@ class SpecializeError(RuntimeError):
 def source(m) -> tuple[str, str]:
   """(kernel name, complete HIP source) of the straight-line kernel for model m."""
   name = f"rt_{codegen.model_hash(m)}"
-  body = codegen.generate(m, name, extern_c=True)
+  # a code object has one k_all: MJHIP_QM_HANDOFF=0 generates it without the qM hand-off and
+  # forwarding (the bundled kernels read the same switch when their context is created)
+  handoff = None if os.environ.get("MJHIP_QM_HANDOFF", "1")[:1] != "0" else False
+  body = codegen.generate(m, name, extern_c=True, handoff=handoff)
   # MJH_TBUF_EXTERN: the per-stage timer pointer gets C linkage, so the library finds it in
   # the code object by name (mjhip_contextLoadKernel) and points it at the context's timers
   # a model with native-solver pairs rounds every operation as the oracle does: the whole
