@@ -405,7 +405,8 @@ MJHIP_API int mjhip_inverseBatch(mjhipContext* c, int B,
  * xfrc_applied are read from the mirror (mjhip_mirrorUpload; zero after context creation).
  * Optional qacc (B x nv) receives the result; every mjData field is in the mirror.
  * Models with activation dynamics or muscle gain/bias are MJHIP_ERR_MODEL here: they go
- * through mjhip_forwardBatchEx, which takes the activations. */
+ * through mjhip_forwardBatchEx, which takes the activations.
+ * (mjhip_forwardSolveBatch, below, is the call that solves constraint rows.) */
 MJHIP_API int mjhip_forwardBatch(mjhipContext* c, int B, const mjtNum* qpos, const mjtNum* qvel,
                                  const mjtNum* ctrl, mjtNum* qacc, int flags, int* status);
 
@@ -551,6 +552,70 @@ MJHIP_API int mjhip_transitionFDBatch(mjhipContext* c, int B, const mjhipTransit
 /* mirror slots a call over B base states needs (-1: NULL context) */
 MJHIP_API long mjhip_transitionFDSlots(const mjhipContext* c, int B, int want_A, int want_B,
                                        int flg_centered);
+
+/* Batched mj_forward with constraint rows (engine_forward.c:1054-1090, skipsensor = 1): the
+ * stages of mjhip_forwardBatchEx up to qacc_smooth, then mj_fwdConstraint (:654-731) with its
+ * warmstart (:536-603) and the Newton solver (engine_solver.c:1722-1891, dense Hessian).
+ * Limits, friction loss, equalities and contacts with the pyramidal cone are solved; an
+ * instance without rows gets qacc = qacc_smooth and niter = 0, and raises no status bit.
+ * mjhip_forwardBatch, mjhip_rolloutBatch and mjhip_transitionFDBatch are unchanged: they still
+ * flag rows MJHIP_INST_UNSUPPORTED.
+ *
+ * Inputs (mjhipSolveIn): the solver options of mjOption (iterations, tolerance, ls_iterations,
+ * ls_tolerance; mjhipOption does not carry them) and mjModel.stat.meaninertia; qpos (B x nq)
+ * and qvel (B x nv) unless MJHIP_FLAG_MIRROR_INPUT; ctrl (B x nu), act (B x na) and
+ * qacc_warmstart (B x nv), each of which may be NULL: the mirror's ctrl and act, and the
+ * context's kept warmstart, which is zero at first use (as after mj_resetData) and holds the
+ * last call's qacc afterwards (:723). qfrc_applied and xfrc_applied are the mirror's. solver
+ * and noslip_iterations sit at the end of the struct: a caller whose size field stops before
+ * them means Newton and 0. The size rule: below offsetof(mjhipSolveIn, solver) (80) is
+ * MJHIP_ERR_ARG; from there up to sizeof(mjhipSolveIn) - 1 the two members are not read; from
+ * sizeof(mjhipSolveIn) on they are, and bytes a later header may add behind them are ignored. Outputs (mjhipSolveOut), all optional: qacc, qfrc_constraint
+ * (B x nv), act_dot, act_next (B x na), niter (B ints: solver_niter[0]). Host arrays, or
+ * device arrays with MJHIP_FLAG_DEVICE_PTRS; status and niter are always host arrays.
+ * Afterwards the mirror holds qacc, qacc_smooth, qfrc_smooth, qfrc_constraint, efc_force,
+ * efc_state and every position- and velocity-stage field.
+ *
+ * status[b] keeps the bad qpos / qvel / qacc bits and what collision and mj_makeConstraint
+ * raised (MJHIP_INST_CNSTRFULL, MJHIP_INST_UNSUPPORTED for a pair); such an instance is not
+ * solved (qacc = qacc_smooth) and the call returns MJHIP_ERR_INSTANCE.
+ * MJHIP_ERR_ARG: a NULL or short struct, iterations <= 0, meaninertia <= 0.
+ * MJHIP_ERR_MODEL (mjhip_forwardSolveCheck): the elliptic cone, the CG and PGS solvers, a
+ * sparse-Jacobian model, noslip_iterations > 0, and what mjhip_forwardBatchEx refuses. */
+typedef enum mjhipSolver_ {          /* mjmodel.h mjtSolver */
+  mjhipSOL_PGS = 0, mjhipSOL_CG, mjhipSOL_NEWTON
+} mjhipSolver;
+typedef struct mjhipSolveIn_ {
+  int size;                      /* sizeof(mjhipSolveIn) as the caller compiled it */
+  int iterations;
+  int ls_iterations;
+  int reserved;
+  mjtNum tolerance;
+  mjtNum ls_tolerance;
+  mjtNum meaninertia;
+  const mjtNum* qpos;
+  const mjtNum* qvel;
+  const mjtNum* ctrl;
+  const mjtNum* act;
+  const mjtNum* qacc_warmstart;
+  int solver;                    /* mjhipSolver; only mjhipSOL_NEWTON is carried */
+  int noslip_iterations;         /* must be 0 */
+} mjhipSolveIn;
+typedef struct mjhipSolveOut_ {
+  int size;                      /* sizeof(mjhipSolveOut) as the caller compiled it */
+  int reserved;
+  mjtNum* qacc;
+  mjtNum* qfrc_constraint;
+  mjtNum* act_dot;
+  mjtNum* act_next;
+  int* niter;
+} mjhipSolveOut;
+MJHIP_API int mjhip_forwardSolveBatch(mjhipContext* c, int B, const mjhipSolveIn* in,
+                                      const mjhipSolveOut* out, int flags, int* status);
+/* the argument and model checks of mjhip_forwardSolveBatch for model m, without a context:
+ * MJHIP_OK, MJHIP_ERR_ARG or MJHIP_ERR_MODEL (mjhip_lastError says why) */
+MJHIP_API int mjhip_forwardSolveCheck(const mjhipModel* m, const mjhipSolveIn* in,
+                                      const mjhipSolveOut* out);
 
 /* copy one mirror field (reference name) of instances [first, first+count) to/from host
  * memory in the reference's per-instance row-major layout (count x fieldSize) */

@@ -30,6 +30,7 @@
 #include "pair_program.h"
 #include "rollout.h"
 #include "transition_call.h"
+#include "solver_call.h"
 // lane-count variants of the cooperative kernel (kern_constraint.hip), measurement only
 extern template __global__ void k_constraint_coop<8, true, false, false>(mjhipModel, Mirror, int, const int*, const int*, const CoopPair*, const mjh::ContactParam*, const unsigned long long*, int, double*, int*);
 extern template __global__ void k_constraint_coop<32, true, false, false>(mjhipModel, Mirror, int, const int*, const int*, const CoopPair*, const mjh::ContactParam*, const unsigned long long*, int, double*, int*);
@@ -550,6 +551,9 @@ struct mjhipContext_ {
   // mjhip_transitionFDBatch's next states (TransitionCall::Y), grown on demand
   double* transition_y = nullptr;
   size_t transition_y_n = 0;
+  // mjhip_forwardSolveBatch's solver scratch (csrc/solver.h), [capacity/64][k][64], with the
+  // kept qacc_warmstart: allocated and zeroed by the context's first solve, freed with it
+  double* solver_scratch = nullptr;
 };
 
 // 1 when the model has activation states or a muscle gain / bias: only then are the arrays
@@ -1048,6 +1052,7 @@ MJHIP_API void mjhip_contextFree(mjhipContext* c) {
   hipFree(c->masks);
   hipFree(c->rollout_scratch);
   hipFree(c->transition_y);
+  hipFree(c->solver_scratch);
   hipFree(c->mirror_buf);
   hipFree(c->dmodel_buf);
   if (c->rt_module) hipModuleUnload(c->rt_module);
@@ -2164,6 +2169,166 @@ MJHIP_API int mjhip_transitionFDBatch(mjhipContext* c, int B, const mjhipTransit
   }
   // host arrays: collect_status synchronizes the stream before the staging buffers go
   return collect_status(c, B, status, status || !dev);
+}
+
+// the part of mjhipSolveIn every caller has (solver and noslip_iterations came after it)
+static constexpr int kSolveInMin = (int)offsetof(mjhipSolveIn, solver);
+
+MJHIP_API int mjhip_forwardSolveCheck(const mjhipModel* m, const mjhipSolveIn* in,
+                                      const mjhipSolveOut* out) {
+  if (!in || in->size < kSolveInMin) {
+    set_error("mjhip_forwardSolveBatch: mjhipSolveIn is NULL or its size field (%d) is below %d",
+              in ? in->size : 0, kSolveInMin);
+    return MJHIP_ERR_ARG;
+  }
+  if (!out || out->size < (int)sizeof(mjhipSolveOut)) {
+    set_error("mjhip_forwardSolveBatch: mjhipSolveOut is NULL or its size field (%d) is below "
+              "%d", out ? out->size : 0, (int)sizeof(mjhipSolveOut));
+    return MJHIP_ERR_ARG;
+  }
+  if (in->iterations <= 0 || !(in->meaninertia > 0)) {
+    set_error("mjhip_forwardSolveBatch: bad argument (iterations %d, meaninertia %g)",
+              in->iterations, in->meaninertia);
+    return MJHIP_ERR_ARG;
+  }
+  if (!m) return MJHIP_OK;
+  const bool full = in->size >= (int)sizeof(mjhipSolveIn);
+  const int solver = full ? in->solver : (int)mjhipSOL_NEWTON;
+  const int noslip = full ? in->noslip_iterations : 0;
+  const char* why = nullptr;
+  if (m->opt.cone == mjhipCONE_ELLIPTIC) why = "the elliptic friction cone";
+  else if (solver != mjhipSOL_NEWTON) why = "a solver other than Newton (CG, PGS)";
+  else if (mjh_isSparse(m)) why = "a sparse constraint Jacobian";
+  else if (noslip > 0) why = "the noslip pass (noslip_iterations > 0)";
+  else why = actuation_unsupported(*m);
+  if (why) {
+    set_error("mjhip_forwardSolveBatch: %s is not supported", why);
+    return MJHIP_ERR_MODEL;
+  }
+  return MJHIP_OK;
+}
+
+MJHIP_API int mjhip_forwardSolveBatch(mjhipContext* c, int B, const mjhipSolveIn* in,
+                                      const mjhipSolveOut* out, int flags, int* status) {
+  if (const int rc = mjhip_forwardSolveCheck(c ? &c->hmodel : nullptr, in, out)) return rc;
+  if (!c) {
+    if (mjhip_deviceCount() <= 0) {
+      set_error("mjhip_forwardSolveBatch: no HIP device (there is no CPU fallback)");
+      return MJHIP_ERR_NO_DEVICE;
+    }
+    set_error("mjhip_forwardSolveBatch: NULL context");
+    return MJHIP_ERR_ARG;
+  }
+  const bool dev = flags & MJHIP_FLAG_DEVICE_PTRS;
+  const bool mirror_in = flags & MJHIP_FLAG_MIRROR_INPUT;
+  if (B < 0 || (!mirror_in && (!in->qpos || !in->qvel))) {
+    set_error("mjhip_forwardSolveBatch: bad argument (B %d; qpos/qvel required without "
+              "MJHIP_FLAG_MIRROR_INPUT)", B);
+    return MJHIP_ERR_ARG;
+  }
+  if (B > c->capacity) {
+    set_error("batch %d exceeds context capacity %d", B, c->capacity);
+    return MJHIP_ERR_CAPACITY;
+  }
+  if (B == 0) return MJHIP_OK;
+  const mjhipModel& m = c->hmodel;
+  HIPCHECK(hipSetDevice(c->device));
+  if (!c->solver_scratch) {
+    const size_t n = (size_t)mjhip_solverScratchDoubles(&m, c->efc_cap) * c->capacity;
+    HIPCHECK(hipMalloc((void**)&c->solver_scratch, sizeof(double)*(n ? n : 1)));
+    HIPCHECK(hipMemsetAsync(c->solver_scratch, 0, sizeof(double)*(n ? n : 1), c->stream));
+  }
+  const size_t nB = (size_t)B;
+  SolverCall call{};
+  call.scratch = c->solver_scratch;
+  call.status = c->status;
+  call.tolerance = in->tolerance;
+  call.ls_tolerance = in->ls_tolerance;
+  call.meaninertia = in->meaninertia;
+  call.iterations = in->iterations;
+  call.ls_iterations = in->ls_iterations;
+  call.B = B;
+  RolloutTemps tmp;
+  int* dniter = nullptr;
+  if (dev) {
+    if (!mirror_in) {
+      call.qpos = in->qpos;
+      call.qvel = in->qvel;
+      call.ctrl = m.nu ? in->ctrl : nullptr;
+      call.act = m.na ? in->act : nullptr;
+    }
+    call.qacc_warmstart = in->qacc_warmstart;
+    call.qacc = out->qacc;
+    call.qfrc_constraint = out->qfrc_constraint;
+    call.act_dot = m.na ? out->act_dot : nullptr;
+    call.act_next = m.na ? out->act_next : nullptr;
+  } else {
+    bool ok = true;
+    auto up = [&](const mjtNum* src, size_t n) -> const double* {
+      if (!src || !n) return nullptr;
+      double* p = tmp.get(n);
+      if (!p || hipMemcpyAsync(p, src, sizeof(double)*n, hipMemcpyHostToDevice, c->stream) !=
+                    hipSuccess) {
+        ok = false;
+        return nullptr;
+      }
+      return p;
+    };
+    auto down = [&](const mjtNum* dst, size_t n) -> double* {
+      if (!dst || !n) return nullptr;
+      double* p = tmp.get(n);
+      if (!p) ok = false;
+      return p;
+    };
+    if (!mirror_in) {
+      call.qpos = up(in->qpos, nB*m.nq);
+      call.qvel = up(in->qvel, nB*m.nv);
+      call.ctrl = up(in->ctrl, nB*m.nu);
+      call.act = up(in->act, nB*m.na);
+    }
+    call.qacc_warmstart = up(in->qacc_warmstart, nB*m.nv);
+    call.qacc = down(out->qacc, nB*m.nv);
+    call.qfrc_constraint = down(out->qfrc_constraint, nB*m.nv);
+    call.act_dot = down(out->act_dot, nB*m.na);
+    call.act_next = down(out->act_next, nB*m.na);
+    if (!ok) {
+      set_error("mjhip_forwardSolveBatch: staging the host arrays on the device failed");
+      return MJHIP_ERR_HIP;
+    }
+  }
+  if (out->niter) {                         // a host array in either mode, as status is
+    dniter = (int*)tmp.get((nB + 1)/2);
+    if (!dniter) {
+      set_error("mjhip_forwardSolveBatch: staging niter on the device failed");
+      return MJHIP_ERR_HIP;
+    }
+    call.niter = dniter;
+  }
+  if (mjhip_launchForwardSolve(c->stream, c->dmodel, c->mirror, call, c->con_cap > 0)) {
+    set_error("mjhip_forwardSolveBatch: kernel launch failed");
+    return MJHIP_ERR_HIP;
+  }
+  if (!dev) {
+    auto get = [&](mjtNum* dst, const double* src, size_t n) {
+      return !dst || !src || !n ||
+             hipMemcpyAsync(dst, src, sizeof(double)*n, hipMemcpyDeviceToHost, c->stream) ==
+                 hipSuccess;
+    };
+    bool ok = get(out->qacc, call.qacc, nB*m.nv);
+    ok = get(out->qfrc_constraint, call.qfrc_constraint, nB*m.nv) && ok;
+    ok = get(out->act_dot, call.act_dot, nB*m.na) && ok;
+    ok = get(out->act_next, call.act_next, nB*m.na) && ok;
+    if (!ok) {
+      set_error("mjhip_forwardSolveBatch: copying the results to the host failed");
+      return MJHIP_ERR_HIP;
+    }
+  }
+  if (dniter) {
+    HIPCHECK(hipMemcpyAsync(out->niter, dniter, sizeof(int)*nB, hipMemcpyDeviceToHost,
+                            c->stream));
+  }
+  // host arrays and niter: collect_status synchronizes the stream before the staging buffers go
+  return collect_status(c, B, status, status || !dev || dniter);
 }
 
 MJHIP_API int mjhip_actuationBatch(mjhipContext* c, int B, const mjtNum* ctrl,

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+import weakref
 
 import numpy as np
 
@@ -117,6 +118,8 @@ SIGNATURES = {
     "mjhip_inverseFD": (None, [_V, _V, ctypes.c_double, ctypes.c_ubyte, _D, _D, _D, _D, _D,
                                _D, _D]),
     "mjhip_releaseModel": (None, [_V]),
+    "mjhip_forwardSolveBatch": (ctypes.c_int, [_V, ctypes.c_int, _V, _V, ctypes.c_int, _V]),
+    "mjhip_forwardSolveCheck": (ctypes.c_int, [_V, _V, _V]),
 }
 
 
@@ -154,6 +157,52 @@ class TransitionOut(ctypes.Structure):
   """mjhipTransitionOut."""
   _fields_ = [("size", ctypes.c_int), ("reserved", ctypes.c_int), ("A", _V), ("B", _V),
               ("C", _V), ("D", _V)]
+
+
+class SolveIn(ctypes.Structure):
+  """mjhipSolveIn."""
+  _fields_ = [("size", ctypes.c_int), ("iterations", ctypes.c_int),
+              ("ls_iterations", ctypes.c_int), ("reserved", ctypes.c_int),
+              ("tolerance", ctypes.c_double), ("ls_tolerance", ctypes.c_double),
+              ("meaninertia", ctypes.c_double), ("qpos", _V), ("qvel", _V), ("ctrl", _V),
+              ("act", _V), ("qacc_warmstart", _V), ("solver", ctypes.c_int),
+              ("noslip_iterations", ctypes.c_int)]
+
+
+class SolveOut(ctypes.Structure):
+  """mjhipSolveOut."""
+  _fields_ = [("size", ctypes.c_int), ("reserved", ctypes.c_int), ("qacc", _V),
+              ("qfrc_constraint", _V), ("act_dot", _V), ("act_next", _V), ("niter", _V)]
+
+
+# stat.meaninertia of models that carry none (bundled .npz files, .mjb files written without
+# statistics), computed once per model object as mj_setConst does; the model is not written
+_meaninertia = weakref.WeakKeyDictionary()
+
+
+def mean_inertia(m):
+  """mjModel.stat.meaninertia: the model's own (setconst.py, or a .mjb file's), else computed."""
+  from . import setconst
+  mi = getattr(m, "stat", {}).get("meaninertia")
+  if mi:
+    return float(mi)
+  if m not in _meaninertia:
+    _meaninertia[m] = setconst.mean_inertia(m)
+  return _meaninertia[m]
+
+
+def solve_options(m, **over):
+  """mjhipSolveIn with the model's solver settings (mjcf.solver_options) and its
+  stat.meaninertia (mean_inertia); keyword arguments override single members."""
+  from . import mjcf
+  sin = SolveIn()
+  sin.size = ctypes.sizeof(SolveIn)
+  for k, v in mjcf.solver_options(m).items():
+    setattr(sin, k, v)
+  sin.meaninertia = mean_inertia(m)
+  for k, v in over.items():
+    setattr(sin, k, v)
+  return sin
 
 
 # the reference's mjtTimer slots (include/mujoco/mjdata.h), mjhipTimer in include/mjhip.h
@@ -590,6 +639,86 @@ class InverseEngine:
                                          st.ctypes.data)
     _check(rc, "mjhip_transitionFDBatch")   # per-instance flags come back in `st`
     return (A, Bm, st) if status else (A, Bm)
+
+  def forward_solve(self, qpos, qvel, ctrl=None, act=None, qacc_warmstart=None,
+                    qfrc_constraint=False, niter=False, status=False, **options):
+    """Batched mj_forward with constraint rows (mjhip_forwardSolveBatch): the smooth stages of
+    forward(), then mj_fwdConstraint with the Newton solver. qpos [B, nq], qvel [B, nv];
+    ctrl [B, nu] and act [B, na] (None: the mirror's); qacc_warmstart [B, nv] (None: the
+    context's kept warmstart, zero at first and the last call's qacc afterwards).
+    qfrc_applied / xfrc_applied are the mirror's (set_field). The solver's settings come from
+    the model (mjcf.solver_options: iterations, tolerance, ls_iterations, ls_tolerance, solver,
+    noslip_iterations) and its stat.meaninertia; keyword arguments of those names override them.
+
+    Returns qacc [B, nv] and then, in this order, those asked for: qfrc_constraint [B, nv],
+    niter [B] (solver_niter[0]), status [B]. An instance without rows gets qacc_smooth and
+    niter 0. Elliptic cones, the CG and PGS solvers, sparse-Jacobian models and the noslip
+    pass raise MJHIPError (MJHIP_ERR_MODEL).
+
+    Host arrays in -> numpy arrays out. Contiguous float64 torch tensors on the context's GPU
+    in -> torch tensors out on that GPU (niter and status are numpy arrays in either case)."""
+    m = self.m
+    nv, nq, na, nu = self.nv, self.nq, m.na, m.nu
+    sin = solve_options(m, **options)
+    sout = SolveOut()
+    sout.size = ctypes.sizeof(SolveOut)
+    dev = _dptr(qpos) is not None
+    opt = (("ctrl", ctrl, nu), ("act", act, na), ("qacc_warmstart", qacc_warmstart, nv))
+    keep = []
+    if dev:
+      import torch
+      B = qpos.shape[0]
+      # the kernel indexes these by B without bounds: check the shapes before the launch
+      if tuple(qpos.shape) != (B, nq) or _dptr(qvel) is None or tuple(qvel.shape) != (B, nv):
+        raise MJHIPError(f"forward_solve: expected qpos [{B}, {nq}] and qvel [{B}, {nv}]")
+      sin.qpos, sin.qvel = _dptr(qpos), _dptr(qvel)
+      for name, arr, n in opt:
+        if arr is None or not n:
+          continue
+        if _dptr(arr) is None or arr.numel() != B * n:
+          raise MJHIPError(f"forward_solve: {name} must be a device tensor of B x {n} = "
+                           f"{B * n} values")
+        setattr(sin, name, _dptr(arr))
+      mk = lambda: torch.empty((B, nv), dtype=torch.float64, device=qpos.device)
+      qacc = mk()
+      qc = mk() if qfrc_constraint else None
+      ptr = _dptr
+    else:
+      qpos = np.ascontiguousarray(qpos, dtype=np.float64).reshape(-1, nq)
+      B = qpos.shape[0]
+      qvel = np.ascontiguousarray(qvel, dtype=np.float64)
+      if qvel.size != B * nv:
+        raise MJHIPError(f"forward_solve: qvel holds {qvel.size} values, expected {B}x{nv}")
+      sin.qpos, sin.qvel = qpos.ctypes.data, qvel.ctypes.data
+      keep += [qpos, qvel]
+      for name, arr, n in opt:
+        if arr is None or not n:
+          continue
+        arr = np.ascontiguousarray(arr, dtype=np.float64)
+        if arr.size != B * n:
+          raise MJHIPError(f"forward_solve: {name} holds {arr.size} values, expected {B}x{n}")
+        setattr(sin, name, arr.ctypes.data)
+        keep.append(arr)
+      qacc = np.zeros((B, nv))
+      qc = np.zeros((B, nv)) if qfrc_constraint else None
+      ptr = lambda a: a.ctypes.data
+    sout.qacc = ptr(qacc)
+    sout.qfrc_constraint = None if qc is None else ptr(qc)
+    ni = np.zeros(B, dtype=np.int32) if niter else None
+    sout.niter = None if ni is None else ni.ctypes.data
+    st = np.zeros(B, dtype=np.int32) if (status or not dev) else None
+    pst = None if st is None else st.ctypes.data
+    if dev:
+      with _TorchOrder(self):
+        rc = lib().mjhip_forwardSolveBatch(self.ctx, B, ctypes.byref(sin), ctypes.byref(sout),
+                                           FLAG_DEVICE_PTRS, pst)
+    else:
+      rc = lib().mjhip_forwardSolveBatch(self.ctx, B, ctypes.byref(sin), ctypes.byref(sout), 0,
+                                         pst)
+    _check(rc, "mjhip_forwardSolveBatch")   # per-instance flags come back in `st`
+    res = [qacc] + ([qc] if qfrc_constraint else []) + ([ni] if niter else []) + \
+        ([st] if status else [])
+    return res[0] if len(res) == 1 else tuple(res)
 
   def actuation(self, B=None, ctrl=None, act=None, status=False):
     """Batched mj_fwdActuation over the actuator_length, actuator_velocity and

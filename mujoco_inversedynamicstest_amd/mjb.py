@@ -377,7 +377,7 @@ def offsets(ints: dict) -> dict:
 #----------------------------------------- read -------------------------------------------
 
 def read_raw(buf: bytes):
-  """Parse an .mjb buffer: (ints, sizes, option dict, {field: array}). The checks and
+  """Parse an .mjb buffer: (ints, sizes, option dict, {field: array}, statistics). The checks and
   messages are mj_loadModelBuffer's."""
   buf = memoryview(bytes(buf))
   n = len(buf)
@@ -413,6 +413,8 @@ def read_raw(buf: bytes):
   for k in OPTION_INTS:
     opt[k] = struct.unpack_from("<i", buf, q)[0]
     q += 4
+  # mjStatistic's first member (mjmodel.h): meaninertia
+  stat = {"meaninertia": struct.unpack_from("<d", buf, p + SIZEOF_OPTION + SIZEOF_VISUAL)[0]}
   p += SIZEOF_OPTION + SIZEOF_VISUAL + SIZEOF_STATISTIC
   arrays = {}
   for name, rows, code, cols in LAYOUT:
@@ -425,7 +427,7 @@ def read_raw(buf: bytes):
     p += nbytes
   if p != n:
     raise MJBError("Model file is too large")
-  return ints, sizes, opt, arrays
+  return ints, sizes, opt, arrays, stat
 
 
 def _names(ints, arrays):
@@ -466,13 +468,17 @@ def unsupported(ints, arrays) -> str | None:
 def read(buf: bytes):
   """mj_loadModelBuffer for the engine: an .mjb buffer -> mjcf.Model."""
   from . import mjcf
-  ints, sizes, opt, arrays = read_raw(buf)
+  ints, sizes, opt, arrays, stat = read_raw(buf)
   why = unsupported(ints, arrays)
   if why:
     raise MJBError(f"model uses {why}, which the MI355X inverse path does not implement")
   m = mjcf.Model()
   m.sizes = {k: int(ints[k]) for k in fields.MODEL_SIZES if k in ints}
   m.opt = opt
+  # the file's statistics; a file written without them (mjb.write) leaves 0: the engine
+  # then computes the value as mj_setConst does (setconst.mean_inertia)
+  if stat["meaninertia"] > 0:
+    m.stat["meaninertia"] = stat["meaninertia"]
   A = {k: v for k, v in arrays.items()}
   try:
     derived = mjcf.sparse_structures(dict(m.sizes), A, jacobian=int(opt["jacobian"]))

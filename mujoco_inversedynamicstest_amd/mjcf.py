@@ -83,6 +83,7 @@ CAMLIGHT = {"fixed": 0, "track": 1, "trackcom": 2, "targetbody": 3, "targetbodyc
 INTEGRATOR = {"Euler": 0, "RK4": 1, "implicit": 2, "implicitfast": 3}
 JACOBIAN = {"dense": 0, "sparse": 1, "auto": 2}
 CONE = {"pyramidal": 0, "elliptic": 1}
+SOLVER = {"PGS": 0, "CG": 1, "Newton": 2}             # mjtSolver
 DISABLE = {"constraint": 0, "equality": 1, "frictionloss": 2, "limit": 3, "contact": 4,
            "passive": 5, "gravity": 6, "clampctrl": 7, "warmstart": 8, "filterparent": 9,
            "actuation": 10, "refsafe": 11, "sensor": 12, "midphase": 13, "eulerdamp": 14,
@@ -511,6 +512,12 @@ class Model:
     self.sizes = {}
     self.opt = {}
     self.names = {}
+    # mjStatistic members the engine uses: meaninertia (setconst.py, or the .mjb file's)
+    self.stat = {}
+    # the constraint solver's settings an MJCF <option> names (solver_options()). They are
+    # kept out of `opt`: codegen.model_hash covers opt's items, and a model's kernels do not
+    # depend on how its rows are solved
+    self.solver_opt = {}
 
   def __getitem__(self, k):
     return getattr(self, k)
@@ -528,6 +535,8 @@ class Model:
             "__sizes_vals": np.array(list(self.sizes.values()), dtype=np.int64)}
     for k, v in self.opt.items():
       arrs["__opt_" + k] = np.asarray(v)
+    for k, v in self.solver_opt.items():
+      arrs["__solveropt_" + k] = np.asarray(v)
     for f in fields.MODEL_FIELDS:
       arrs[f.name] = getattr(self, f.name)
     for k, v in self.names.items():
@@ -543,6 +552,9 @@ class Model:
       if k.startswith("__opt_"):
         v = z[k]
         m.opt[k[6:]] = v.tolist() if v.ndim else (int(v) if v.dtype.kind == "i" else float(v))
+      elif k.startswith("__solveropt_"):
+        v = z[k]
+        m.solver_opt[k[12:]] = int(v) if v.dtype.kind == "i" else float(v)
       elif k.startswith("__names_"):
         lst = [str(x) for x in z[k]]
         m.names[k[8:]] = [] if lst == [""] and m.sizes.get(_NAME_SIZE.get(k[8:], ""), 0) == 0 else lst
@@ -565,6 +577,19 @@ class Model:
       # alias every actuator to act[0])
       m.actuator_actadr, m.actuator_actnum = activation_addresses(m.actuator_dyntype)
     return m
+
+
+# mj_defaultOption's constraint-solver settings (engine_io.c; mjb.OPTION_DEFAULTS has the same)
+SOLVER_DEFAULTS = {"solver": 2, "iterations": 100, "tolerance": 1e-8, "ls_iterations": 50,
+                   "ls_tolerance": 0.01, "noslip_iterations": 0}
+
+
+def solver_options(m) -> dict:
+  """The model's constraint-solver settings: m.solver_opt's (what an MJCF <option> names),
+  else m.opt's (a .mjb file's mjOption, which mjb.read keeps whole), else
+  mj_defaultOption's."""
+  own = getattr(m, "solver_opt", {})
+  return {k: type(v)(own.get(k, m.opt.get(k, v))) for k, v in SOLVER_DEFAULTS.items()}
 
 
 def activation_addresses(dyntype):
@@ -604,6 +629,7 @@ class MJCFCompiler:
                 "o_friction": [1.0, 1.0, 0.005, 0.0001, 0.0001],
                 "integrator": 0, "cone": 0, "jacobian": 2, "disableflags": 0,
                 "enableflags": 0, "ccd_tolerance": 1e-6, "ccd_iterations": 50}
+    self.solver_opt = {}
     self.classes = {}
     self.bodies = []
     self.tendons = []
@@ -1082,6 +1108,19 @@ class MJCFCompiler:
         o[k] = float(a[k])
     if "ccd_iterations" in a:
       o["ccd_iterations"] = int(a["ccd_iterations"])
+    # the constraint solver's settings (mjhip_forwardSolveBatch takes them per call), in a
+    # dict of their own; solver_options() supplies the default of a key not given
+    so = self.solver_opt
+    for k in ("tolerance", "ls_tolerance"):
+      if k in a:
+        so[k] = float(a[k])
+    for k in ("iterations", "ls_iterations", "noslip_iterations"):
+      if k in a:
+        so[k] = int(a[k])
+    if "solver" in a:
+      if a["solver"] not in SOLVER:
+        raise MJCFError(f"unknown solver '{a['solver']}'")
+      so["solver"] = SOLVER[a["solver"]]
     for k in ("gravity", "wind", "magnetic", "o_solref", "o_solimp", "o_friction"):
       if k in a:
         o[k] = _floats(a[k])
@@ -2400,6 +2439,7 @@ class MJCFCompiler:
     A.update(sparse_structures(s, A, jacobian=int(self.opt["jacobian"])))
     # scalars and names
     m.opt = {k: (list(v) if isinstance(v, list) else v) for k, v in self.opt.items()}
+    m.solver_opt = dict(self.solver_opt)
     for k, v in A.items():
       setattr(m, k, v)
     arr("body_subtreemass", nbody, np.float64)

@@ -364,6 +364,19 @@ def wrap(x0, x1, xpos, xmat, r, wtype, side):
   return xmat @ r0 + xpos, xmat @ r1 + xpos, wlen
 
 
+def mean_inertia(m, e=None):
+  """mjModel.stat.meaninertia as mj_setConst computes it (engine_setconst.c:545-552); 1, the
+  value of mj_defaultStatistic (engine_io.c:288), for a model without dofs."""
+  if not m.nv:
+    return 1.0
+  if e is None:
+    e = _Eval(m, m.qpos0.astype(np.float64))
+  s = 0.0
+  for i in range(m.nv):
+    s += float(e.M[i, i])
+  return s / m.nv
+
+
 def set_const(m):
   """Fill the compile-time constants of `m` in place (mj_setConst subset)."""
   nv, nb = m.nv, m.nbody
@@ -376,6 +389,8 @@ def set_const(m):
   # dof_M0 (mj_setM0): armature + cdof_i . (crb_i cdof_i)
   for i in range(nv):
     m.dof_M0[i] = m.dof_armature[i] + e.cdof[i] @ (e.crb[m.dof_bodyid[i]] @ e.cdof[i])
+  # stat.meaninertia (engine_setconst.c:545-552): the mean diagonal of qM at qpos0
+  m.stat = dict(getattr(m, "stat", {}), meaninertia=mean_inertia(m, e))
   Minv = np.linalg.inv(e.M) if nv else np.zeros((0, 0))
   # body_invweight0
   m.body_invweight0[:] = 0
